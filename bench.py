@@ -24,11 +24,18 @@ that workload -- 1 048 576 arms SHARDED over the N GPUs ("scaling": "strong") --
 (1 048 576 arms per GPU) and BASELINE.json configs[3] (4 194 304 arms sharded), each per-step and fused.  At N = 1 strong and
 weak are the same job.  --envs-per-gpu / --envs-total pick another headline.
 
-Timing protocol (robust to short --steps; `measure()`): a time-based pre-warm brings the GPU to its steady clock, then W
-untimed warm-up steps, the running episode is ended so that a region starts an episode (N = 1) or half-way through one (N > 1:
-the region's RCCL exchange then runs beside the steps behind the episode end; --episode-phase), then the region of EXACTLY K
-steps -- bracketed by barrier + torch.cuda.synchronize() on both sides, max over ranks -- is run `repeats` times; `ms_per_step` /
-`value` come from the MEDIAN region (min / max beside it).  Beside the wall clock every region is bracketed by HIP events on
+A plain run measures the headline only: set-up, warm-up, ONE timed region of exactly K steps, the JSON line.  Everything
+else -- the roofline (HIP-event step laps inside the timed regions, the mt_stream_probe yardstick), the secondary
+configurations, the N > 1 legs, the CPU baseline -- and the repeated regions of the headline run with --full, as a plain run
+did before it existed.  --dump-outputs DIR writes what the timed steps computed as DIR/<name>.npy (dump_outputs()).
+
+Timing protocol (`measure()`): a time-based pre-warm brings the GPU to its steady clock, then the episode loop starts over
+from episode 0 (so that what follows does not depend on how many pre-warm steps fitted into the time), W untimed warm-up
+steps, the running episode is ended so that a region starts an episode (N = 1) or half-way through one (N > 1: the region's
+RCCL exchange then runs beside the steps behind the episode end; --episode-phase), then the region of EXACTLY K steps --
+bracketed by barrier + torch.cuda.synchronize() on both sides, max over ranks -- is run `repeats` times (1 in a plain run; with
+--full enough regions for >= 250 ms of GPU work, robust to short --steps); `ms_per_step` / `value` come from the MEDIAN region
+(min / max beside it).  Beside the wall clock every region is bracketed by HIP events on
 the engine's streams (mt_timer_start / mt_timer_stop_async: from the idle device at the region's start to the end of its last
 kernel, reset or exchange, no host wait in between): `value_device_timeline` is the same throughput on that clock, i.e. without
 the host latency of the two fences, which at 8 GPUs x 131 072 arms is a third of a 20-step region.  The device time of a STEP
@@ -37,7 +44,8 @@ streams that stay forked across calls; a lap begins with the first of them and e
 says so).  Where mt_rollout takes the episode's reset into its first launch (small shards), that launch -- another kernel --
 is issued as a rollout call of its own outside the laps, inside the region and its device timeline (EpisodeLoop.head_steps).
 The laps are a stopwatch inside the timed work (two event records per lap, 7 us): every LAP_EVERY-th region carries them, the
-others run the same calls without; `value` is the median over all regions, `config.ms_per_step_lapped_regions` beside it.
+others run the same calls without; `value` is the median over all regions, `config.ms_per_step_lapped_regions` beside it.  A
+plain run takes no laps (they only feed the roofline of --full).
 
 Prints ONE JSON line on rank 0 (contract: see the task brief / DESIGN.md section "Measurement").
 """
@@ -61,6 +69,10 @@ MIN_TIMED_S = 0.25           # the repeated timed regions together cover at leas
 LAP_EVERY = 4                   # bench.measure: every 4th timed region carries the HIP-event step laps (see there)
 PREWARM_S = 0.3
 F_LAST_RETURN = 12           # mt_field MT_F_LAST_RETURN (include/manytor_hip.h): the return an env had when it was last reset
+DUMP_BYTES = 60 * 10 ** 6     # --dump-outputs: at most this much in all ...
+DUMP_RETURNS = 1 << 20       # ... of which the gathered returns of at most this many envs (a fixed, seeded sample) ...
+DUMP_SAMPLE = 1 << 17        # ... and the per-env fields of at most this many (fewer where K and D make a row wide)
+DUMP_SEED = 0x5EED
 
 
 def algorithmic_bytes_per_env_step(dof, k):
@@ -264,6 +276,13 @@ class EpisodeLoop:
         self.eng.reset_random(seed, 0)
 
     phase = 0                   # steps of the running episode already done when a timed region starts (--episode-phase)
+
+    def restart(self):
+        """Start over at step 0 of episode 0 with every env reset, as the constructor did: what the loop computes from here
+        on does not depend on how many steps ran before (bench.measure's pre-warm is time-based)."""
+        self.step = 0
+        self.episode = 0
+        self.eng.reset_random(self.seed, 0)
 
     def align(self):
         """End the running episode now (gather + reset, as at a regular episode end), so that the next step is the first of
@@ -553,13 +572,51 @@ def rollout_steps_per_launch(raw):
         return 1
 
 
+def dump_sample(n, cap):
+    """Indices of a fixed, seeded sample of at most `cap` of n items, ascending (all of them when n <= cap)."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=cap, replace=False))
+
+
+def dump_outputs(out_dir, raw, returns):
+    """--dump-outputs: what the timed steps computed, as out_dir/<name>.npy in float32 (float64 for env ids), at most
+    DUMP_BYTES in all.  `returns`: every env's episode return as the loop gathered it last -- what the loop hands its
+    caller.  Beside it the engine's per-env fields as the timed steps left them: obs, reward, done, end effector, joint angles
+    (goals), alive masks, targets, running returns.  Where the last timed step ends an episode the reset behind it is part
+    of the timed work, so these fields then hold the start of the next episode.  Large batches are written for a fixed,
+    seeded sample of envs (`env_ids`, `returns_env_ids`: global ids).  With the same arguments the inputs are the same from
+    run to run (seeded device streams; measure() restarts the loop after its time-based pre-warm), so two builds can be
+    compared file by file.  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    ridx = dump_sample(len(returns), DUMP_RETURNS)
+    arrays = {"returns": np.asarray(returns, dtype=np.float32)[ridx]}
+    if len(ridx) < len(returns):
+        arrays["returns_env_ids"] = ridx.astype(np.float64)
+    fields = (("obs", raw.obs), ("reward", raw.reward), ("done", raw.done), ("ee", raw.ee), ("goals", raw.goals),
+              ("alive", raw.alives), ("points", raw.points), ("total_reward", raw.total_reward))
+    host = {name: get() for name, get in fields}
+    per_env = 8 + sum(4 * (a.size // raw.n_envs) for a in host.values())
+    room = DUMP_BYTES - sum(a.nbytes for a in arrays.values())
+    idx = dump_sample(raw.n_envs, min(DUMP_SAMPLE, room // per_env))
+    arrays["env_ids"] = (idx + raw.env_id_base).astype(np.float64)
+    for name, a in host.items():
+        arrays[name] = a[idx].astype(np.float32)
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def measure(fab, raw, n_total, steps, warmup, episode_len, seed, fused=False, overlap=True, repeats=0, prewarm_s=PREWARM_S,
-            min_timed_s=MIN_TIMED_S):
+            min_timed_s=MIN_TIMED_S, laps=True):
     """The timing protocol of the contract on one engine (this rank's shard; gather already attached): time-based
-    pre-warm, `warmup` untimed steps, then `repeats` regions of EXACTLY `steps` steps, each bracketed by fence() on both
-    sides; the region time is the max over ranks, the figure the median region.  Every region is also bracketed by HIP
-    events on the engine's streams (device idle after the opening fence -> end of the region's last kernel / reset /
-    exchange): `region_device_ms`, max over ranks, median.  Returns a dict of raw numbers."""
+    pre-warm, a restart of the episode loop, `warmup` untimed steps, then `repeats` regions (0: enough for `min_timed_s`) of
+    EXACTLY `steps` steps, each bracketed by fence() on both sides; the region time is the max over ranks, the figure the
+    median region.  Every region is also bracketed by HIP events on the engine's streams (device idle after the opening
+    fence -> end of the region's last kernel / reset / exchange): `region_device_ms`, max over ranks, median.  laps = False:
+    no HIP-event step laps in any region (the step_us figures are None then).  Returns a dict of raw numbers, and under
+    "returns" the host copy of the episode returns gathered last."""
     eng = TimedEngine(raw)
     L = max(1, min(episode_len, steps))                         # >= 1 gather inside every timed region
     loop = EpisodeLoop(eng, seed, L, fused=fused, overlap=overlap, steps_per_launch=rollout_steps_per_launch(raw),
@@ -573,6 +630,7 @@ def measure(fab, raw, n_total, steps, warmup, episode_len, seed, fused=False, ov
         raw.sync()
     est_s = float(fab.max_over_ranks([(time.perf_counter() - t0) / max(1, prewarm) * steps])[0])   # one region, estimated
     reps = repeats or int(min(300, max(5, math.ceil(min_timed_s / max(est_s, 1e-6)))))
+    loop.restart()                                              # the same inputs from here on, however long the pre-warm ran
     loop.run(warmup)                                            # the W untimed warm-up steps of the contract
     loop.align()                                                # the first timed region starts an episode
     fab.fence(raw)
@@ -580,10 +638,10 @@ def measure(fab, raw, n_total, steps, warmup, episode_len, seed, fused=False, ov
     # The step laps are a stopwatch INSIDE the timed work: an event record in front of and behind the launches of every lap,
     # 7 us per lap (tools/lap_cost.py) -- 1 % of a 20-step region of 1 M arms, 10 % of one of a 131 072-arm shard (two laps).
     # Every LAP_EVERY-th region carries them (same calls, same launches in all regions), the others run without.
-    lap_every = LAP_EVERY if reps >= 3 * LAP_EVERY else 1
+    lap_every = (LAP_EVERY if reps >= 3 * LAP_EVERY else 1) if laps else 0
     lapped = []
     for rep in range(reps):
-        with_laps = rep % lap_every == 0
+        with_laps = laps and rep % lap_every == 0
         eng.start_region()
         fab.fence(raw)
         raw.timer_start()                                       # start mark on the idle device (ahead of the host clock)
@@ -611,20 +669,26 @@ def measure(fab, raw, n_total, steps, warmup, episode_len, seed, fused=False, ov
     assert np.all(g == np.round(g)) and np.abs(g).max() <= L    # returns of an L-step episode
     elapsed = float(np.median(regions))
     lap_mask = np.asarray(lapped, dtype=bool)
-    elapsed_lapped = float(np.median(np.asarray(regions)[lap_mask]))     # the regions that carried the stopwatch
     dev_s = float(np.median(device_ms)) * 1e-3
-    step_us = float(np.median(step_us_regions))                 # median over regions: one stalled lap does not move it
+    if laps:
+        elapsed_lapped = float(np.median(np.asarray(regions)[lap_mask]))     # the regions that carried the stopwatch
+        step_us = float(np.median(step_us_regions))             # median over regions: one stalled lap does not move it
+        step_us_max, ms_lapped = float(np.max(step_us_regions)), elapsed_lapped / steps * 1e3
+    else:
+        step_us = step_us_max = ms_lapped = None
+    # in line, the gather is timed by the laps only
+    gather_us = gather_ms * 1e3 / max(1, gathers) if (loop.overlap or laps) else None
     return {"elapsed": elapsed, "ms_per_step": elapsed / steps * 1e3, "ms_per_step_min": float(regions.min()) / steps * 1e3,
             "ms_per_step_max": float(regions.max()) / steps * 1e3, "step_us": step_us,
-            "step_us_max_region": float(np.max(step_us_regions)),
-            "launches": launches, "gather_us": gather_ms * 1e3 / max(1, gathers), "gathers_per_region": gathers // reps,
+            "step_us_max_region": step_us_max,
+            "launches": launches, "gather_us": gather_us, "gathers_per_region": gathers // reps,
             "repeats": reps, "prewarm": prewarm, "episode_len": L, "value": n_total * steps / elapsed,
             "region_device_ms": dev_s * 1e3, "device_ms_per_step": dev_s * 1e3 / steps,
             "value_device_timeline": n_total * steps / max(dev_s, 1e-12),
-            "steps_per_kernel_launch": launches / max(1, loop.kernel_launches),
+            "steps_per_kernel_launch": launches / max(1, loop.kernel_launches) if laps else None,   # counted in the laps
             "episode_first_launches_outside_laps": loop.head_launches, "episode_first_launch_steps": loop.head_steps,
             "lapped_regions": int(lap_mask.sum()), "laps_every_nth_region": lap_every,
-            "ms_per_step_lapped_regions": elapsed_lapped / steps * 1e3}
+            "ms_per_step_lapped_regions": ms_lapped, "returns": g}
 
 
 def self_launch(argv, gpus, dry_run=False, timeout_s=1800.0, script=None):
@@ -728,7 +792,15 @@ def main():
     ap.add_argument("--dof", type=int, default=4, choices=(4, 7))
     ap.add_argument("--targets", type=int, default=7)
     ap.add_argument("--episode-len", type=int, default=50)       # test_multi.py:8
-    ap.add_argument("--repeats", type=int, default=0, help="timed regions (0 = enough for >= 250 ms of GPU work, 5..300)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of exactly --steps steps each (0 = enough for >= 250 ms of GPU work, 5..300).  "
+                         "Default: 1 (the run times exactly --steps steps); 0 with --full")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: repeated timed regions, the roofline (HIP-event step laps, "
+                         "mt_stream_probe yardstick), the secondary configurations or N > 1 legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float32 / float64; a fixed, "
+                         "seeded sample of envs for large batches; see dump_outputs)")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED)
     ap.add_argument("--sync-gather", action="store_true",
                     help="run the return gather in line on the engine's stream instead of overlapped on its side stream")
@@ -741,8 +813,8 @@ def main():
                          "and the exchange runs beside the p steps behind it).  Default: 0 on one GPU (nothing to hide: "
                          "40.9 vs 42.0 us per step, profiles/r03_ab_episode_phase.txt), half an episode with N > 1 (the "
                          "RCCL all-gather of a region is then hidden behind steps instead of waited for at the fence)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: without the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: without the secondary configurations / legs")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="torch.distributed backend of the CONTROL plane for N > 1 (barrier, max over ranks, shipping "
                          "the RCCL unique id); the return gather itself always goes through mt_gather_returns = RCCL, "
@@ -931,10 +1003,14 @@ def main():
     else:
         strong, n_total = world > 1, 1048576     # one GPU: strong and weak are the same job (reported as "weak", as before)
     raw, n_local, gather_fallback = make_engine(n_total, strong)
+    repeats = args.repeats if args.repeats is not None else (0 if args.full else 1)
     r = measure(fab, raw, n_total, args.steps, args.warmup, args.episode_len, args.seed, fused=args.fused,
-                overlap=not args.sync_gather, repeats=args.repeats)
+                overlap=not args.sync_gather, repeats=repeats, laps=args.full)
     if args.ablate:
         print("ABLATION BUILD: timings only, outputs are not the reference's", file=sys.stderr)
+    if args.dump_outputs and rank == 0:
+        shapes = dump_outputs(args.dump_outputs, raw, r["returns"])
+        print(f"[bench] outputs of the timed steps in {args.dump_outputs}: {shapes}", file=sys.stderr)
     L = r["episode_len"]
     kernel_name = raw.step_kernel_name()
     dispatch = raw.dispatch()
@@ -942,14 +1018,6 @@ def main():
 
     out = None
     if rank == 0:
-        step_s = r["step_us"] * 1e-6                            # device time of one step of this rank's envs (HIP events)
-        # mt_rollout may run a step as several concurrent launches on env ranges (the dispatch says so)
-        chains = 1 if args.fused else int(dispatch["rollout"]["chains"])
-        envs_per_launch = n_local if chains == 1 else int(dispatch["chains"]["span"])
-        spl = r["steps_per_kernel_launch"]                      # 1 = one launch per step; L for --fused; k on small shards
-        moved = moved_bytes_per_env_step(args.dof, args.targets, spl)
-        achieved = moved * n_local / step_s / 1e9
-        achieved_model = bpe * n_local / step_s / 1e9
         trig = 2 if args.hw_trig else (1 if args.direct_trig else 0)
         static = not (args.no_specialize or args.dh_in_lds)
         table_name = ("Ref4Table" if args.dof == 4 else "Dh7Table") if static else f"RtTable<{args.dof}>"
@@ -958,9 +1026,6 @@ def main():
                                            ("dh_in_lds", args.dh_in_lds)) if on)
         workload = f"{n_total} arms in all = {n_local} arms/GPU x {world} GPU, {args.dof}-DoF DH chain, K={args.targets} targets, " \
                    f"25 sub-steps, random integer-degree actions drawn in-kernel, episode {L} steps"
-        # the streaming yardstick of the step's own access shape: pure HBM (4 M envs, ~1 GB per pass) and at this size
-        ach_hbm = achievable_bandwidth(m, args.dof, args.targets, 4194304, dev)
-        ach_same = achievable_bandwidth(m, args.dof, args.targets, max(256, n_local), dev)
         out = {
             "metric": METRIC, "value": r["value"], "unit": "env-steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"],
@@ -971,18 +1036,12 @@ def main():
                        "targets": args.targets, "substeps": 25, "episode_len": L, "episode_phase": EpisodeLoop.phase % L,
                        "collective": describe_collective(gather_fallback),
                        "kernel_variant": variant, "prewarm_launches": r["prewarm"], "repeats": r["repeats"],
-                       "laps_every_nth_region": r["laps_every_nth_region"], "lapped_regions": r["lapped_regions"],
-                       "ms_per_step_lapped_regions": r["ms_per_step_lapped_regions"],
-                       "laps_note": "the HIP-event laps that time the step launches (roofline.avg_kernel_us) are a stopwatch inside "
-                                    "the timed work: an event record in front of and behind each lap's launches, 7 us per lap "
-                                    "(tools/lap_cost.py).  Every laps_every_nth_region-th region carries them, the others run the "
-                                    "same calls and launches without; ms_per_step / value are the median over ALL regions, "
-                                    "ms_per_step_lapped_regions the median of those with the stopwatch",
                        "gathers_in_timed_region": r["gathers_per_region"], "gather_mode": gather_mode(gather_fallback),
                        "launcher": os.environ.get("TORCHELASTIC_RUN_ID") and "torch.distributed.run" or
                                    ("bench.py self_launch (one fresh child process per rank)" if world > 1 else "none (one process)"),
-                       "timing": "median over `repeats` regions of exactly `steps` steps, each bracketed by "
-                                 "torch.cuda.synchronize() + barrier (device drained, then every rank arrived), max over ranks; value_device_timeline = the same regions on the "
+                       "timing": "median over `repeats` regions of exactly `steps` steps (one region unless --full or "
+                                 "--repeats), each bracketed by torch.cuda.synchronize() + barrier (device drained, then every "
+                                 "rank arrived), max over ranks; value_device_timeline = the same regions on the "
                                  "device's clock (HIP events from the idle device at the region's start to the end of its "
                                  "last kernel / reset / exchange, max over ranks, median)",
                        "barrier": "none (one rank)" if world == 1 else
@@ -992,7 +1051,28 @@ def main():
                        "dispatch": {k: dispatch[k] for k in ("step", "chains", "rollout", "fused", "reset", "overrides")}},
             "ms_per_step_min": r["ms_per_step_min"], "ms_per_step_max": r["ms_per_step_max"],
             "gather_us": r["gather_us"],
-            "roofline": {
+        }
+    if rank == 0 and args.full:
+        step_s = r["step_us"] * 1e-6                            # device time of one step of this rank's envs (HIP events)
+        # mt_rollout may run a step as several concurrent launches on env ranges (the dispatch says so)
+        chains = 1 if args.fused else int(dispatch["rollout"]["chains"])
+        envs_per_launch = n_local if chains == 1 else int(dispatch["chains"]["span"])
+        spl = r["steps_per_kernel_launch"]                      # 1 = one launch per step; L for --fused; k on small shards
+        moved = moved_bytes_per_env_step(args.dof, args.targets, spl)
+        achieved = moved * n_local / step_s / 1e9
+        achieved_model = bpe * n_local / step_s / 1e9
+        # the streaming yardstick of the step's own access shape: pure HBM (4 M envs, ~1 GB per pass) and at this size
+        ach_hbm = achievable_bandwidth(m, args.dof, args.targets, 4194304, dev)
+        ach_same = achievable_bandwidth(m, args.dof, args.targets, max(256, n_local), dev)
+        out["config"].update({
+                       "laps_every_nth_region": r["laps_every_nth_region"], "lapped_regions": r["lapped_regions"],
+                       "ms_per_step_lapped_regions": r["ms_per_step_lapped_regions"],
+                       "laps_note": "the HIP-event laps that time the step launches (roofline.avg_kernel_us) are a stopwatch inside "
+                                    "the timed work: an event record in front of and behind each lap's launches, 7 us per lap "
+                                    "(tools/lap_cost.py).  Every laps_every_nth_region-th region carries them, the others run the "
+                                    "same calls and launches without; ms_per_step / value are the median over ALL regions, "
+                                    "ms_per_step_lapped_regions the median of those with the stopwatch"})
+        out["roofline"] = {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBS,
                 "traffic": load_traffic(f"d{args.dof}_k{args.targets}_n{n_local}", spl),
@@ -1031,9 +1111,8 @@ def main():
                         "step is two CONCURRENT launches of envs_per_launch envs on two streams: rocprofv3's per-launch "
                         "average is then the duration of each of two overlapping kernels, not half a step; the union of "
                         "their intervals per step (tools/trace_summary.py --union) corresponds to avg_kernel_us",
-            },
         }
-    secondary = world == 1 and not args.fused and not args.ablate and not args.no_secondary
+    secondary = args.full and world == 1 and not args.fused and not args.ablate and not args.no_secondary
     if secondary and rank == 0:
         # informational, not the headline: the same episodes as ONE launch each
         us, _ = time_step_launches(m, n_local, table, radius, args.targets, dev, args.seed, fused=True, steps=1000)
@@ -1100,7 +1179,7 @@ def main():
                 rec["achievable_gbs"] = out["roofline"]["achievable_gbs"]
                 rec["frac_of_achievable"] = gbs / out["roofline"]["achievable_gbs"]
             out["secondary"]["other_configs"][label] = rec
-    if world > 1 and not args.fused and not args.ablate and not args.no_secondary:
+    if args.full and world > 1 and not args.fused and not args.ablate and not args.no_secondary:
         # One N > 1 invocation yields every figure BASELINE.json's north_star names: the headline is the metric's 1 M arms
         # sharded over these ranks; here the weak leg (1 M arms PER GPU) and configs[3] (4 194 304 arms sharded), each
         # through mt_rollout and as fused segments.  Collective code: every rank runs every leg.
@@ -1118,7 +1197,7 @@ def main():
                                         "scaling.  value = wall clock of the fenced regions; value_device_timeline = the same "
                                         "regions on the device's clock (what the GPUs sustain once the host's fences are out "
                                         "of the picture: a learner that does not fence every 20 steps sees this one)")
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # rank 0 times the CPU ports (every host core it may use); its peers wait asleep, not spinning on those cores
         if rank == 0:
             out["cpu_baseline"] = cpu_baseline(table, args.targets)

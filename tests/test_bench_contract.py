@@ -1,10 +1,11 @@
-"""bench.py's output contract (GPU): ONE JSON line with the keys the driver parses, sane values, and the roofline /
-cpu_baseline objects -- run as the driver runs it (a subprocess), on a reduced batch so it takes seconds."""
+"""bench.py's output contract (GPU): ONE JSON line with the keys the driver parses, sane values, and with --full the
+roofline / cpu_baseline objects -- run as the driver runs it (a subprocess), on a reduced batch so it takes seconds."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,7 +29,7 @@ def test_bench_line_with_its_secondary_legs_holds_no_fraction_above_one():
     key that names a fraction is one, also where the launches move less than SURVEY's model bytes (7-DoF table, k steps per
     launch), where the model-bytes fraction is withheld instead of exceeding 1."""
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                          "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout)
     seen = list(_fractions(d))
@@ -40,7 +41,8 @@ def test_bench_line_with_its_secondary_legs_holds_no_fraction_above_one():
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
-                          "--envs-per-gpu", "262144", "--no-secondary"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+                          "--envs-per-gpu", "262144", "--full", "--no-secondary"], capture_output=True, text=True, timeout=300,
+                         cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.count("\n") == 1 and out.stdout.endswith("\n")     # nothing but the line (native chatter -> stderr)
     d = json.loads(out.stdout)
@@ -88,3 +90,37 @@ def test_bench_prints_one_contract_line():
         assert key in c, key
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 1e4
     assert c["numpy_multiprocess_value"] is not None and c["numpy_multiprocess_value"] > 1e3, c["numpy_multiprocess_sample"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_times_exactly_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain run (no --full) times ONE region of exactly --steps steps and prints the headline only; --dump-outputs writes
+    the timed steps' results as float32 / float64 .npy files under 64 MB, the same in two runs with the same arguments."""
+    dumps = []
+    for run in range(2):
+        dump = tmp_path / f"run{run}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "30", "--warmup", "5",
+                              "--envs-per-gpu", "262144", "--dump-outputs", str(dump)],
+                             capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert out.returncode == 0, out.stderr[-2000:]
+        assert out.stdout.count("\n") == 1
+        d = json.loads(out.stdout)
+        assert d["metric"] == "env-steps/sec (whole node), 1M parallel 4-DoF arms, random actions"
+        assert d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["steps"] == 30 and d["warmup"] == 5 and d["config"]["repeats"] == 1
+        assert d["value"] == pytest.approx(262144 / (d["ms_per_step"] * 1e-3), rel=1e-6)
+        assert d["ms_per_step_min"] == d["ms_per_step"] == d["ms_per_step_max"]
+        for key in ("roofline", "secondary", "cpu_baseline"):
+            assert key not in d, key
+        files = sorted(os.listdir(dump))
+        assert {"returns.npy", "env_ids.npy", "obs.npy", "reward.npy", "done.npy", "ee.npy"} <= set(files)
+        arrays = {f: np.load(dump / f, allow_pickle=False) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(os.path.getsize(dump / f) for f in files) <= 64 * 10 ** 6
+        assert arrays["returns.npy"].shape == (262144,) and arrays["obs.npy"].shape == (131072, 21)
+        # 30 steps = an episode of 30 steps (episode_len = min(50, steps)): whole-number returns of at most 30 in magnitude
+        r = arrays["returns.npy"]
+        assert np.all(r == np.round(r)) and np.abs(r).max() <= 30 and np.any(r != 0)
+        dumps.append(arrays)
+    for f, a in dumps[0].items():
+        np.testing.assert_array_equal(a, dumps[1][f], err_msg=f)

@@ -7,8 +7,7 @@ echo "== $steps"
 for rep in 1 2; do
 for cfg in "lazy+inplace::--reset-before-gather" "lazy+snapshot::" "eager+inplace:MT_LAZY_CHAINS=0:--reset-before-gather" "eager+snapshot:MT_LAZY_CHAINS=0:"; do
   name=${cfg%%:*}; rest=${cfg#*:}; envv=${rest%%:*}; flag=${rest#*:}
-  env $envv python bench.py --gpus 1 $steps --no-secondary --no-cpu-baseline $flag > gpurun_out/ab_$name.json 2>/dev/null
-  python -c "
-import json
-d=json.load(open('gpurun_out/ab_$name.json')); r=d['roofline']; print('$name', round(d['value']/1e10,4), round(d['ms_per_step']*1e3,2), round(r['avg_kernel_us'],2), round(d['gather_us'],1))"
+  env $envv python bench.py --gpus 1 $steps --full --no-secondary --no-cpu-baseline $flag 2>/dev/null | python -c "
+import json, sys
+d=json.loads(sys.stdin.read()); r=d['roofline']; print('$name', round(d['value']/1e10,4), round(d['ms_per_step']*1e3,2), round(r['avg_kernel_us'],2), round(d['gather_us'],1))"
 done; done; done

@@ -4,7 +4,7 @@
 for rep in 1 2; do
   for c in 0 4 5 6; do
     echo -n "[cap $c] bench: "
-    MT_FLAT_BLOCKS_PER_CU=$c python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('value %.4g  wall_us %.2f  device_us %.2f  frac %.3f' % (d['value'], d['ms_per_step']*1e3, d['roofline']['avg_kernel_us'], d['roofline']['frac']))"
+    MT_FLAT_BLOCKS_PER_CU=$c python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('value %.4g  wall_us %.2f  device_us %.2f  frac %.3f' % (d['value'], d['ms_per_step']*1e3, d['roofline']['avg_kernel_us'], d['roofline']['frac']))"
   done
 done
 for rep in 1 2; do

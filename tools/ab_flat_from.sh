@@ -10,6 +10,6 @@ done
 for rep in 1 2 3; do
   for ff in 0 1000000000; do
     echo -n "bench MT_FLAT_FROM=$ff "
-    MT_FLAT_FROM=$ff python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['achieved'], d['roofline']['frac'])"
+    MT_FLAT_FROM=$ff python bench.py --gpus 1 --steps 20 --warmup 5 --full --no-cpu-baseline --no-secondary 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['achieved'], d['roofline']['frac'])"
   done
 done

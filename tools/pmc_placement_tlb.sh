@@ -5,7 +5,7 @@ set -e
 out=$1
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$out"
-run() { name=$1; shift; timeout -k 10 400 rocprofv3 --pmc "$@" --output-format csv -d "$out/$name" -- python3 bench.py --no-cpu-baseline --steps 20 --warmup 5 > "$out/$name.json" 2> "$out/$name.err"; }
+run() { name=$1; shift; timeout -k 10 400 rocprofv3 --pmc "$@" --output-format csv -d "$out/$name" -- python3 bench.py --full --no-cpu-baseline --steps 20 --warmup 5 > "$out/$name.json" 2> "$out/$name.err"; }
 run utcl1 TCP_UTCL1_REQUEST_sum TCP_UTCL1_TRANSLATION_HIT_sum TCP_UTCL1_TRANSLATION_MISS_sum
 run grbm GRBM_GUI_ACTIVE GRBM_UTCL2_BUSY
 run lat TCP_TCC_READ_REQ_LATENCY_sum TCP_TCC_WRITE_REQ_LATENCY_sum TCP_PENDING_STALL_CYCLES_sum

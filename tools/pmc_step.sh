@@ -5,7 +5,7 @@ set -e
 out=$1; shift
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$out"
-run() { name=$1; shift; timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d "$out/$name" -- python3 bench.py --no-cpu-baseline --steps 60 --warmup 10 $BENCH_ARGS > "$out/$name.json" 2> "$out/$name.err"; }
+run() { name=$1; shift; timeout -k 10 300 rocprofv3 --pmc "$@" --output-format csv -d "$out/$name" -- python3 bench.py --full --no-cpu-baseline --steps 60 --warmup 10 $BENCH_ARGS > "$out/$name.json" 2> "$out/$name.err"; }
 BENCH_ARGS="$*"
 run fetch FETCH_SIZE
 run write WRITE_SIZE

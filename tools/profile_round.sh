@@ -6,7 +6,7 @@ tag=$1
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/prof_$tag
 mkdir -p "$out"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline > "$out/bench_under_trace.json" 2> "$out/trace.err"
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- python3 bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > "$out/bench_under_trace.json" 2> "$out/trace.err"
 find "$out/trace" -name "*kernel_stats.csv" -exec cp {} "$out/kernel_stats.csv" \;
 head -12 "$out/kernel_stats.csv"
 trace_csv=$(find "$out/trace" -name "*kernel_trace.csv" | head -1)

@@ -12,7 +12,7 @@ if [ ! -f "$lib" ] || [ tests/fake_rccl/fake_rccl.cpp -nt "$lib" ]; then
 fi
 port=$((20000 + RANDOM % 20000))
 MT_RCCL_LIB=$PWD/$lib HSA_ENABLE_IPC_MODE_LEGACY=0 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 \
-  --nproc-per-node "$ranks" --master-addr 127.0.0.1 --master-port "$port" bench.py --gpus "$ranks" --steps 20 --warmup 5 \
+  --nproc-per-node "$ranks" --master-addr 127.0.0.1 --master-port "$port" bench.py --gpus "$ranks" --steps 20 --warmup 5 --full \
   --single-device --backend gloo "$@" > "$out" 2> "${out%.json}.err"
 python - "$out" <<'PY'
 import json, sys

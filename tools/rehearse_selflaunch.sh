@@ -12,7 +12,7 @@ if [ ! -f "$lib" ] || [ tests/fake_rccl/fake_rccl.cpp -nt "$lib" ]; then
   /opt/rocm/bin/hipcc -O1 -std=c++17 -fPIC -shared tests/fake_rccl/fake_rccl.cpp -o "$lib" -lrt
 fi
 unset WORLD_SIZE RANK LOCAL_RANK MASTER_ADDR MASTER_PORT
-MT_RCCL_LIB=$PWD/$lib timeout -k 10 900 python3 bench.py --gpus "$ranks" --steps 20 --warmup 5 --single-device --backend gloo "$@" \
+MT_RCCL_LIB=$PWD/$lib timeout -k 10 900 python3 bench.py --gpus "$ranks" --steps 20 --warmup 5 --full --single-device --backend gloo "$@" \
   > "$out" 2> "${out%.json}.err"
 python3 - "$out" <<'PY'
 import json, sys
