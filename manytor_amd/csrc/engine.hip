@@ -355,8 +355,10 @@ static void choose_dispatch(mt_handle h) {
 
 // whole_rows: the launch covers the batch or a 256-aligned range of it (not the single-env view), so threads past the
 // end of the range may read on to the end of their block inside the rows (what the TT kernels do before their barrier)
+// codes: the handle's target codes are valid (engine_internal.h, codes_valid); h->codes_valid is left true only where the
+// launch reads (and so keeps) them
 template <class Tbl, bool LDS_OK>
-void launch_step_t(mt_handle h, const StepArgs& args, bool sample, bool whole_rows) {
+void launch_step_t(mt_handle h, const StepArgs& args, bool sample, bool whole_rows, bool codes) {
   const dim3 g = grid_for(args.n), b(kBlock);
 #define MT_LAUNCH_STEP(SAMPLE_, TRIG_, LDS_) \
   hipLaunchKernelGGL((step_kernel<Tbl, SAMPLE_, TRIG_, LDS_>), g, b, 0, h->stream, args)
@@ -396,12 +398,18 @@ void launch_step_t(mt_handle h, const StepArgs& args, bool sample, bool whole_ro
   }
   if constexpr (ActionTrigTable<Tbl>::value) {
     if (tt) {
-      if (h->prefetch && args.n >= h->flat_from)  // HBM-bound launches: kernels.h, LaneOffset<false>; see step_blocks_per_cu
-        hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, true, true>), g, b,
-                           lds_pad_for_blocks(step_blocks_per_cu(h, args.n), kTrigEntries * sizeof(SinCos)), h->stream, args);
+      const size_t pad = h->prefetch ? lds_pad_for_blocks(step_blocks_per_cu(h, args.n), kTrigEntries * sizeof(SinCos)) : 0;
+      // the prefetch kernels read the targets as their codes while those are valid (kernels.h, CODES: 28 B per env less)
+      if (h->prefetch && codes) {
+        if (args.n >= h->flat_from)
+          hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, true, true, false, true>), g, b, pad, h->stream, args);
+        else
+          hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, true, false, false, true>), g, b, pad, h->stream, args);
+        h->codes_valid = true;
+      } else if (h->prefetch && args.n >= h->flat_from)  // HBM-bound launches: kernels.h, LaneOffset<false>; see step_blocks_per_cu
+        hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, true, true>), g, b, pad, h->stream, args);
       else if (h->prefetch)
-        hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, true>), g, b,
-                           lds_pad_for_blocks(step_blocks_per_cu(h, args.n), kTrigEntries * sizeof(SinCos)), h->stream, args);
+        hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, true>), g, b, pad, h->stream, args);
       else
         hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, 0, true>), g, b, 0, h->stream, args);
       return;
@@ -440,10 +448,11 @@ bool launch_step_fresh_t(mt_handle h, const StepArgs& args) {
     return false;
   } else {
     if (h->trig != 0 || !h->trig_steps || h->split || h->lds_table || h->trace) return false;
-    const size_t stage = (size_t)3 * args.K * kBlock * sizeof(float), fixed = kTrigEntries * sizeof(SinCos) + 512;
+    const size_t stage = (size_t)2 * args.K * kBlock * sizeof(float), fixed = kTrigEntries * sizeof(SinCos) + 512;
     if (stage + fixed > 65536) return false;  // (K > 20: above the default dynamic-LDS limit)
     const dim3 g = grid_for(args.n), b(kBlock);
     const size_t lds = std::max(stage, h->prefetch ? lds_pad_for_blocks(step_blocks_per_cu(h, args.n), fixed) : (size_t)0);
+    h->codes_valid = false;  // the drawn targets are written as floats only
     if (h->prefetch && args.n >= h->flat_from)
       hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, true, true, true>), g, b, lds, h->stream, args);
     else if (h->prefetch)
@@ -462,7 +471,7 @@ bool launch_step_fresh(mt_handle h, const StepArgs& args) {
 
 template <int D>
 void launch_step_d(mt_handle h, const StepArgs& args, bool sample, bool whole_rows) {
-  launch_step_t<RtTable<D>, true>(h, args, sample, whole_rows);
+  launch_step_t<RtTable<D>, true>(h, args, sample, whole_rows, false);
 }
 
 template <int D>
@@ -505,12 +514,14 @@ void launch_step_frames_d(mt_handle h, const StepArgs& args, bool sample) {
 // matching view of the sub-step trace buffer or NULL.
 void launch_step(mt_handle h, const StepArgs& args, float* trace, bool sample, bool whole_rows) {
   if (trace) MT_DISPATCH_D(h->D, launch_trace_d, h, args, trace, sample);  // first: it needs the previous pose
+  const bool codes = h->codes_valid;
+  h->codes_valid = false;  // every step kernel may zero targets; only the ones that read codes zero those too
   if (h->custom_frames) {
     MT_DISPATCH_D(h->D, launch_step_frames_d, h, args, sample);
     return;
   }
-  if (h->static_kind == 1) return launch_step_t<Ref4Table, false>(h, args, sample, whole_rows);
-  if (h->static_kind == 2) return launch_step_t<Dh7Table, false>(h, args, sample, whole_rows);
+  if (h->static_kind == 1) return launch_step_t<Ref4Table, false>(h, args, sample, whole_rows, codes);
+  if (h->static_kind == 2) return launch_step_t<Dh7Table, false>(h, args, sample, whole_rows, codes);
   MT_DISPATCH_D(h->D, launch_step_d, h, args, sample, whole_rows);
 }
 
@@ -590,6 +601,7 @@ StepArgs args_for_env(mt_handle h, int64_t env) {
   a.actions += env;
   a.goals += env;
   a.points += env;
+  a.codes += env;
   a.alive += env;
   a.total_reward += env;
   a.obs += env;
@@ -614,6 +626,7 @@ StepArgs args_for_range(mt_handle h, const StepArgs& base, int64_t off, int64_t 
   a.actions += off;
   a.goals += off;
   a.points += off;
+  a.codes += off;
   a.alive += off;
   a.total_reward += off;
   a.obs += off;
@@ -633,7 +646,7 @@ StepArgs args_for_range(mt_handle h, const StepArgs& base, int64_t off, int64_t 
 
 template <int D, bool RANDOM, bool ONLY_DONE>
 void launch_reset_k(mt_handle h, const StepArgs& args) {
-  const size_t lds = RANDOM ? (size_t)3 * args.K * kBlock * sizeof(float) : 0;  // staging columns of the drawn targets
+  const size_t lds = RANDOM ? (size_t)2 * args.K * kBlock * sizeof(float) : 0;  // staging columns of the drawn target codes
   if (lds > 65536)
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&reset_kernel<D, RANDOM, ONLY_DONE>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -644,12 +657,14 @@ template <int D, bool ONLY_DONE>
 void launch_reset_split(mt_handle h, const StepArgs& args) {  // whole batch, small: 4 lanes per env for the draw
   constexpr int L = 4;
   const int64_t per_block = kBlock / L;
-  const size_t lds = (size_t)3 * args.K * per_block * sizeof(float);
+  const size_t lds = (size_t)2 * args.K * per_block * sizeof(float);
   hipLaunchKernelGGL((reset_split_kernel<D, ONLY_DONE, L>), dim3((unsigned)((args.n + per_block - 1) / per_block)),
                      dim3(kBlock), lds, h->stream, args, h->cfg.radius);
 }
 template <int D>
 void launch_reset_d(mt_handle h, const StepArgs& args, int mode) {  // 0 given points, 1 random, 2 random only-done
+  // (the random forms write codes with the targets they draw; a full reset of the whole batch makes them valid: its caller)
+  if (mode == 0) h->codes_valid = false;
   if (mode != 0 && h->reset_split && args.n == h->n)
     return mode == 1 ? launch_reset_split<D, false>(h, args) : launch_reset_split<D, true>(h, args);
   if (mode == 0)
@@ -700,6 +715,7 @@ void launch_rollout_t(mt_handle h, const StepArgs& a, int split, const RolloutAr
 }
 
 void launch_rollout(mt_handle h, const StepArgs& a, int split, const RolloutArgs& r, bool early = false) {
+  h->codes_valid = false;  // the rollout kernels write targets as floats only
   if (h->static_kind == 1) return early ? launch_rollout_t<Ref4Table, kPrefetch>(h, a, split, r) : launch_rollout_t<Ref4Table, 0>(h, a, split, r);
   if (h->static_kind == 2) return early ? launch_rollout_t<Dh7Table, kPrefetch>(h, a, split, r) : launch_rollout_t<Dh7Table, 0>(h, a, split, r);
   switch (h->D) {
@@ -936,7 +952,8 @@ int mt_create(mt_handle* out, const mt_config* cfg) {
                o_done = take(ld), o_bits = take(ld / 64 * 8), o_ee = take(3 * ld * 4), o_epi = take(ld * 4),
                o_last = take(ld * 4), o_ring = take((size_t)cfg->return_ring * ld * 4), o_misc = take(256),
                o_trace = take((cfg->flags & MT_FLAG_TRACE) ? (size_t)cfg->substeps * 3 * ld * 4 : 0),
-               o_zmin = take((cfg->flags & MT_FLAG_DEBUG_ZMIN) ? ld * 4 : 0), o_trig = take(kTrigEntries * sizeof(SinCos));
+               o_zmin = take((cfg->flags & MT_FLAG_DEBUG_ZMIN) ? ld * 4 : 0), o_trig = take(kTrigEntries * sizeof(SinCos)),
+               o_codes = take(2 * K * ld * 4);
   h->arena_bytes = off;
   // (One experiment with hipExtMallocWithFlags(hipDeviceMallocContiguous) instead -- a physically contiguous arena -- cost 5 %
   // at 1 M arms and was dropped the same day: profiles/r04_variants.md section 3.)
@@ -950,6 +967,7 @@ int mt_create(mt_handle* out, const mt_config* cfg) {
   a.actions = (float*)(base + o_act);
   a.goals = (float*)(base + o_goal);
   a.points = (float*)(base + o_pts);
+  a.codes = (uint32_t*)(base + o_codes);
   a.obs = (float*)(base + o_obs);
   a.alive = (uint32_t*)(base + o_alive);
   a.total_reward = (float*)(base + o_tot);
@@ -976,6 +994,7 @@ int mt_create(mt_handle* out, const mt_config* cfg) {
   a.K = h->K;
   a.S = cfg->substeps;
   a.tol = cfg->pickup_tol;
+  a.radius = cfg->radius;
   a.inv_sm1 = 1.0f / (float)(cfg->substeps - 1);
   a.flags = cfg->flags & ~kFlagWholeGoals;  // the internal bit is the host's to set (resets / sampled steps), never the caller's
   a.dh = make_dh(cfg->dh_table, h->D);
@@ -1207,6 +1226,7 @@ static int launch_reset_random(mt_handle h, uint64_t seed, uint32_t episode, int
     h->stream = root;
     if (rc == MT_OK) rc = check_launch(h, "reset_kernel (per chain)");
     if (rc) return rc;
+    h->codes_valid = !h->points_exposed;  // every chain's range drew its targets: codes and floats
     h->is_reset = true;
     return settle_chains(h);
   }
@@ -1215,6 +1235,7 @@ static int launch_reset_random(mt_handle h, uint64_t seed, uint32_t episode, int
   MT_DISPATCH_D(h->D, launch_reset_d, h, h->args, mode);
   rc = check_launch(h, "reset_kernel");
   if (rc) return rc;
+  if (mode == 1) h->codes_valid = !h->points_exposed;  // (a re-arm keeps them as they were: it rewrites what it draws)
   h->is_reset = true;
   return MT_OK;
 }
@@ -1720,6 +1741,7 @@ int mt_rollout(mt_handle h, int n_steps, uint64_t seed, uint32_t step_idx0) {
   }
   if (graph) {
     const mt_engine::RolloutGraph* rg = nullptr;
+    h->codes_valid = false;  // captured launches are replayed whatever the codes' state: the float kernels
     int rc = rollout_graph(h, n_steps, seed, chains, &rg);
     if (rc) return rc;
     if (chains > 1) {
@@ -1964,8 +1986,10 @@ int mt_set(mt_handle h, int field, const void* src, int64_t src_bytes) {
     if (field == MT_F_GOALS) {
       hipLaunchKernelGGL((env_major_to_soa<float>), g, b, 0, h->stream, (const float*)h->staging, h->D, h->n, a.goals, h->ld);
       h->args.flags &= ~kFlagWholeGoals;
-    } else if (field == MT_F_POINTS)
+    } else if (field == MT_F_POINTS) {
       hipLaunchKernelGGL((env_major_to_soa<float>), g, b, 0, h->stream, (const float*)h->staging, 3 * h->K, h->n, a.points, h->ld);
+      h->codes_valid = false;  // anybody's floats: no codes for them
+    }
     else if (field == MT_F_RETURN_RING)
       hipLaunchKernelGGL((env_major_to_soa<float>), g, b, 0, h->stream, (const float*)h->staging, (int)a.ring_slots, h->n, a.ring, h->ld);
     else
@@ -2000,6 +2024,10 @@ int mt_device_ptr(mt_handle h, int field, void** ptr, int64_t* rows, int64_t* ld
     // angle is a whole degree (kFlagWholeGoals: table look-ups for the pose a step starts from) ends here, for good
     h->goals_exposed = true;
     h->args.flags &= ~kFlagWholeGoals;
+  }
+  if (field == MT_F_POINTS) {  // the same for the targets: the step kernels read the floats from now on
+    h->points_exposed = true;
+    h->codes_valid = false;
   }
   *ptr = fi.ptr;
   if (rows) *rows = fi.rows;

@@ -55,6 +55,12 @@ struct mt_engine {
   bool prefetch_forced = false;
   bool prefetch = false;  // step_kernel<..., PF = kPrefetch>: target loads requested ahead of the kinematics
   bool goals_exposed = false;  // mt_device_ptr(MT_F_GOALS) was handed out: joint angles may change without the library knowing
+  // The target codes (StepArgs::codes) match MT_F_POINTS for every env: set by a full random reset (it writes both), kept by
+  // the re-arm of finished envs and by the step launches that read codes (step_kernel<.., CODES>), cleared by everything else
+  // that writes targets (mt_reset, mt_set, the other step / rollout kernels, a deferred reset).  Launches read codes only
+  // while it holds; points_exposed (mt_device_ptr(MT_F_POINTS): floats may change behind the library's back) ends it for good.
+  bool codes_valid = false;
+  bool points_exposed = false;
   bool trig_steps = false;  // step kernels with TT: end-pose sines / cosines from the whole-degree table (static tables, sampled actions)
   int static_kind = 0;   // 0 runtime table, 1 Ref4Table, 2 Dh7Table
   mt_comm* comm = nullptr;

@@ -292,9 +292,62 @@ __device__ __forceinline__ bool within_box(const float (&e)[3], float x, float y
   return (fabsf(e[0] - x) <= tol) && (fabsf(e[1] - y) <= tol) && (fabsf(e[2] - z) <= tol);
 }
 
+// A target's coordinates out of its three 21-bit Philox fields (philox.h candidate_fields): x = 2r u(fx) - r,
+// y = 2r u(fy) - r, z = r u(fz).  Contraction is off so that every op rounds once, exactly as the numpy restatement
+// (oracle/philox_ref.py) does.
+__device__ __forceinline__ void target_coords(uint32_t fx, uint32_t fy, uint32_t fz, float radius, float& x, float& y, float& z) {
+#pragma clang fp contract(off)
+  const float r2 = 2.0f * radius;
+  const float tx = r2 * u21(fx);
+  const float ty = r2 * u21(fy);
+  x = tx - radius;
+  y = ty - radius;
+  z = radius * u21(fz);
+}
+
+// Target code: the three fields in 63 bits of two words, lo = fx | fy << 21, hi = fy >> 11 | fz << 10 -- 8 bytes per
+// target instead of 12.  Every target the library draws is such a triple, so decode_target gives back the float bits of
+// the draw (it IS target_coords).  The dead target (0, 0, 0) is the code of (2^20, 2^20, 0) (2r * 1/2 - r = +0, r * 0 =
+// +0), the draw's fallback point (0, 0, r / 2) that of (2^20, 2^20, 2^20).  Internal rows of the arena (StepArgs::codes,
+// [2K][ld]), valid while the host knows them to match MT_F_POINTS (engine_internal.h: codes_valid).
+struct TargetCode {
+  uint32_t lo, hi;
+};
+__device__ __forceinline__ TargetCode encode_target(uint32_t fx, uint32_t fy, uint32_t fz) {
+  return TargetCode{fx | (fy << 21), (fy >> 11) | (fz << 10)};
+}
+__device__ __forceinline__ void decode_target(TargetCode c, float radius, float& x, float& y, float& z) {
+  target_coords(c.lo & 0x1FFFFFu, (c.lo >> 21) | ((c.hi & 0x3FFu) << 11), c.hi >> 10, radius, x, y, z);
+}
+constexpr uint32_t kHalfField = 1u << 20;  // u21 = 1/2
+constexpr TargetCode kZeroTargetCode{kHalfField, kHalfField >> 11};
+constexpr TargetCode kFallbackTargetCode{kHalfField, (kHalfField >> 11) | (kHalfField << 10)};
+
+// One rejection-sampling candidate of manytor.py:229-239: half HALF of a Philox block (philox.h: two candidates
+// per block), its coordinates and (if asked for) its code.
+template <int HALF>
+__device__ __forceinline__ bool target_candidate(const u32x4& w, float radius, float& x, float& y, float& z,
+                                                 TargetCode* code = nullptr) {
+#pragma clang fp contract(off)
+  uint32_t fx, fy, fz;
+  candidate_fields<HALF>(w, fx, fy, fz);
+  if (code) *code = encode_target(fx, fy, fz);
+  const float rr = radius * radius;
+  target_coords(fx, fy, fz, radius, x, y, z);
+  const float xx = x * x, yy = y * y, zz = z * z;
+  const float sxy = xx + yy;
+  const float n2 = sxy + zz;
+  return n2 <= rr;
+}
+
+// A code parked in a float LDS stage (draw_targets_wave, reset_split_kernel): its two words, `stride` floats apart.
+__device__ __forceinline__ TargetCode staged_code(const float* cell, int stride) {
+  return TargetCode{__float_as_uint(cell[0]), __float_as_uint(cell[stride])};
+}
+
 // One target inside step(): obs2 triple (taken before the pickup, manytor.py:204), pickup test
-// (manytor.py:206), and the zeroing of a target that died earlier (manytor.py:148).
-template <bool ABLATE_OBS, bool R>
+// (manytor.py:206), and the zeroing of a target that died earlier (manytor.py:148) -- with CODES its code as well.
+template <bool ABLATE_OBS, bool CODES = false, bool R>
 __device__ __forceinline__ void step_target(const StepArgs& a, int64_t ld, LaneOffset<R>& o4, int k, uint32_t am, uint32_t& nam,
                                             const float (&el)[3], const float (&e)[3], float x, float y, float z) {
   const bool al = (am >> k) & 1u;
@@ -313,6 +366,11 @@ __device__ __forceinline__ void step_target(const StepArgs& a, int64_t ld, LaneO
     str(row, o4, 0.f);
     str(row + ld, o4, 0.f);
     str(row + 2 * ld, o4, 0.f);
+    if (CODES) {
+      uint32_t* crow = a.codes + (int64_t)(2 * k) * ld;
+      str(crow, o4, kZeroTargetCode.lo);
+      str(crow + ld, o4, kZeroTargetCode.hi);
+    }
   }
   float* orow = a.obs + (int64_t)(3 * k) * ld;
   str_stream(orow, o4, dist);
@@ -767,13 +825,18 @@ __device__ __forceinline__ void draw_targets_wave(uint64_t seed, uint64_t env0, 
 //            the targets with reset_kernel's wave-cooperative draw into LDS columns and writes them out -- reset_kernel's
 //            state, bit for bit, without its launch, without its stores of what this step overwrites anyway (pose, alive
 //            mask, return, end effector, reward, done: 41 B per env) and without this step's loads of what it would have
-//            written (108 B per env).  Dynamic LDS: [3K][kBlock] floats.
-template <class Tbl, bool SAMPLE, int TRIG, bool LDS, int PF = 0, bool TT = false, bool FLAT = false, bool FRESH = false>
+//            written (108 B per env).  Dynamic LDS: [2K][kBlock] target codes.
+//   CODES  : the targets are read as their 8-byte codes (StepArgs::codes, kernels.h TargetCode) instead of the 12 bytes of
+//            their floats: 56 instead of 84 B per env at K = 7, of the 233 a step moves.  Only while the host knows the codes
+//            to match MT_F_POINTS (engine_internal.h: codes_valid); a dead target's code is zeroed with its floats.
+template <class Tbl, bool SAMPLE, int TRIG, bool LDS, int PF = 0, bool TT = false, bool FLAT = false, bool FRESH = false,
+          bool CODES = false>
 __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) void step_kernel(const StepArgs a) {
   constexpr int D = Tbl::D;
   static_assert(!TT || (SAMPLE && TRIG == 0 && !LDS && ActionTrigTable<Tbl>::value), "the table serves sampled actions of a static table");
   static_assert(!FRESH || TT, "the reset prologue exists for the sampled-action kernels of the static tables");
-  extern __shared__ float fresh_stage[];                          // FRESH: the drawn targets, [3K][kBlock]
+  static_assert(!CODES || (PF && TT && !FRESH), "codes are read by the prefetch kernels of the static tables");
+  extern __shared__ float fresh_stage[];                          // FRESH: the drawn target codes, [2K][kBlock]
   __shared__ uint8_t fresh_slots[FRESH ? kBlock / 64 : 1][64];    // FRESH: draw_targets_wave's scratch
   __shared__ DhConst sh;
   __shared__ __attribute__((aligned(16))) SinCos trig_lds[TT ? kTrigEntries : 1];
@@ -804,6 +867,7 @@ __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) voi
 #pragma unroll
   for (int j = 0; j < D; ++j) g[j] = FRESH ? 0.f : ldr(a.goals + j * ld, o4);
   float tx[PF ? PF : 1][3];
+  uint32_t tc[CODES ? PF : 1][2];
   if constexpr (FRESH) {
     const bool mine = i < a.n;
     const uint32_t lane = threadIdx.x & 63u;
@@ -818,13 +882,18 @@ __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) voi
 #pragma unroll
       for (int k = 0; k < (PF ? PF : 0); ++k)
         if (k < a.K) {
+          decode_target(staged_code(col + 2 * k * kBlock, kBlock), a.radius, tx[k][0], tx[k][1], tx[k][2]);
 #pragma unroll
-          for (int q = 0; q < 3; ++q) {
-            tx[k][q] = col[(3 * k + q) * kBlock];
-            str(a.points + (int64_t)(3 * k + q) * ld, o4, tx[k][q]);
-          }
+          for (int q = 0; q < 3; ++q) str(a.points + (int64_t)(3 * k + q) * ld, o4, tx[k][q]);
         }
-      for (int r = 3 * PF; r < 3 * a.K; ++r) str(a.points + (int64_t)r * ld, o4, col[r * kBlock]);
+      for (int k = PF; k < a.K; ++k) {
+        float x, y, z;
+        decode_target(staged_code(col + 2 * k * kBlock, kBlock), a.radius, x, y, z);
+        const int64_t r = 3 * k;
+        str(a.points + r * ld, o4, x);
+        str(a.points + (r + 1) * ld, o4, y);
+        str(a.points + (r + 2) * ld, o4, z);
+      }
     }
   } else if (PF) {
 #pragma unroll
@@ -834,9 +903,15 @@ __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) voi
         // certainly issued behind the one it waits for -- so the kinematics starts once nearly all prefetched rows are back.
         // Unconditional loads, the last row again for the slots past K, give exact counts and were measured: +2 % at
         // 98 304-131 072 envs, nothing elsewhere: profiles/r03_ab_unconditional_prefetch.txt.)
-        const float* row = a.points + (int64_t)(3 * k) * ld;
+        if constexpr (CODES) {
+          const uint32_t* crow = a.codes + (int64_t)(2 * k) * ld;
+          tc[k][0] = ldr(crow, o4);
+          tc[k][1] = ldr(crow + ld, o4);
+        } else {
+          const float* row = a.points + (int64_t)(3 * k) * ld;
 #pragma unroll
-        for (int q = 0; q < 3; ++q) tx[k][q] = ldr(row + q * ld, o4);
+          for (int q = 0; q < 3; ++q) tx[k][q] = ldr(row + q * ld, o4);
+        }
       }
   }
   // The alive mask and the return are requested now, ahead of the arithmetic that does not need them.
@@ -893,7 +968,10 @@ __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) voi
   if (PF) {
 #pragma unroll
     for (int k = 0; k < PF; ++k)
-      if (k < a.K) step_target<false>(a, ld, o4, k, am, nam, el, e, tx[k][0], tx[k][1], tx[k][2]);
+      if (k < a.K) {
+        if constexpr (CODES) decode_target(TargetCode{tc[k][0], tc[k][1]}, a.radius, tx[k][0], tx[k][1], tx[k][2]);
+        step_target<false, CODES>(a, ld, o4, k, am, nam, el, e, tx[k][0], tx[k][1], tx[k][2]);
+      }
   }
   for (int k = PF; k < a.K; ++k) {
     if (TRIG == 5) {  // DIAGNOSTIC: arithmetic only, no HBM traffic for targets / observations
@@ -902,6 +980,13 @@ __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) voi
       observe_target(el, x, y, z, dist, r, th);
       if (within_box(e, x, y, z, a.tol)) nam &= ~(1u << k);
       if (dist + r + th == -12345.0f) (a.obs + (int64_t)(3 * k) * ld)[i] = dist;
+      continue;
+    }
+    if constexpr (CODES) {
+      const uint32_t* crow = a.codes + (int64_t)(2 * k) * ld;
+      float x, y, z;
+      decode_target(TargetCode{ldr(crow, o4), ldr(crow + ld, o4)}, a.radius, x, y, z);
+      step_target<false, true>(a, ld, o4, k, am, nam, el, e, x, y, z);
       continue;
     }
     const float* row = a.points + (int64_t)(3 * k) * ld;
@@ -1224,26 +1309,6 @@ __global__ __launch_bounds__(kBlock) void done_bits_rebuild_kernel(const uint8_t
   if ((threadIdx.x & 63) == 0 && (int64_t)i < n) done_bits[i >> 6] = bits;
 }
 
-// One rejection-sampling candidate of manytor.py:229-239: half HALF of a Philox block (philox.h: two candidates
-// per block).  Contraction is off so that every op rounds once, exactly as the numpy restatement
-// (oracle/philox_ref.py) does.
-template <int HALF>
-__device__ __forceinline__ bool target_candidate(const u32x4& w, float radius, float& x, float& y, float& z) {
-#pragma clang fp contract(off)
-  uint32_t fx, fy, fz;
-  candidate_fields<HALF>(w, fx, fy, fz);
-  const float r2 = 2.0f * radius;
-  const float rr = radius * radius;
-  const float tx = r2 * u21(fx);
-  const float ty = r2 * u21(fy);
-  x = tx - radius;
-  y = ty - radius;
-  z = radius * u21(fz);
-  const float xx = x * x, yy = y * y, zz = z * z;
-  const float sxy = xx + yy;
-  const float n2 = sxy + zz;
-  return n2 <= rr;
-}
 
 // Rejection-sample K targets for one env (manytor.py:229-239) and hand each accepted one to `put(k, x, y, z)`.
 // Candidates are taken in the order (block 0, half 0), (block 0, half 1), (block 1, half 0), ...
@@ -1292,15 +1357,14 @@ __global__ __launch_bounds__(kBlock) void sample_actions_kernel(float* actions, 
 // block blk_T + r), the accepted candidates are numbered in (block, half) order with two ballots and written straight
 // into T's LDS column.  That is exactly the sequential order of draw_targets, so the targets are the same bits; the wave
 // finishes in ~9 trips instead of ~13, and a reset_done with few finished envs in one or two.
-// `need` = this lane's env wants targets; `col0` = the LDS column of the wave's lane 0 ([3K][kBlock] floats per block).
+// `need` = this lane's env wants targets; `col0` = the LDS column of the wave's lane 0 ([2K][kBlock] target codes per block).
 __device__ __forceinline__ void draw_targets_wave(uint64_t seed, uint64_t env0, uint32_t episode, bool need, int K, float radius,
                                                   float* col0, uint8_t* slots) {
   const uint32_t lane = threadIdx.x & 63u;
-  auto put = [&](uint32_t t, int k, float x, float y, float z) {
-    float* cell = col0 + t + 3 * k * kBlock;
-    cell[0] = x;
-    cell[kBlock] = y;
-    cell[2 * kBlock] = z;
+  auto put = [&](uint32_t t, int k, TargetCode c) {  // (the stage is float: the words travel as bit patterns, never as values)
+    float* cell = col0 + t + 2 * k * kBlock;
+    cell[0] = __uint_as_float(c.lo);
+    cell[kBlock] = __uint_as_float(c.hi);
   };
   int cnt = need ? 0 : K;
   uint32_t blk = 0;
@@ -1311,8 +1375,9 @@ __device__ __forceinline__ void draw_targets_wave(uint64_t seed, uint64_t env0, 
       if (cnt < K) {
         const u32x4 w = stream_block(seed, env0 + lane, kTagTarget, episode, blk);
         float x, y, z;
-        if (target_candidate<0>(w, radius, x, y, z)) put(lane, cnt++, x, y, z);
-        if (cnt < K && target_candidate<1>(w, radius, x, y, z)) put(lane, cnt++, x, y, z);
+        TargetCode c;
+        if (target_candidate<0>(w, radius, x, y, z, &c)) put(lane, cnt++, c);
+        if (cnt < K && target_candidate<1>(w, radius, x, y, z, &c)) put(lane, cnt++, c);
         ++blk;
       }
     } else {
@@ -1330,19 +1395,20 @@ __device__ __forceinline__ void draw_targets_wave(uint64_t seed, uint64_t env0, 
       const uint32_t epT = (uint32_t)__shfl((int)episode, (int)T);
       bool a0 = false, a1 = false;
       float x0 = 0.f, y0 = 0.f, z0 = 0.f, x1 = 0.f, y1 = 0.f, z1 = 0.f;
+      TargetCode c0{0u, 0u}, c1{0u, 0u};
       if (serving) {
         const u32x4 w = stream_block(seed, env0 + T, kTagTarget, epT, blkT + r);
-        a0 = target_candidate<0>(w, radius, x0, y0, z0);
-        a1 = target_candidate<1>(w, radius, x1, y1, z1);
+        a0 = target_candidate<0>(w, radius, x0, y0, z0, &c0);
+        a1 = target_candidate<1>(w, radius, x1, y1, z1, &c1);
       }
       const unsigned long long A0 = __ballot(a0), A1 = __ballot(a1);
       auto group_mask = [&](uint32_t grp) { return (h == 64u ? ~0ull : ((1ull << h) - 1ull)) << (grp * h); };
       if (serving) {  // number my candidates behind those of the lower lanes of my group: (block, half) order
         const unsigned long long lower = group_mask(g) & ((1ull << lane) - 1ull);
         const int k0 = cntT + __popcll(A0 & lower) + __popcll(A1 & lower);
-        if (a0 && k0 < K) put(T, k0, x0, y0, z0);
+        if (a0 && k0 < K) put(T, k0, c0);
         const int k1 = k0 + (a0 ? 1 : 0);
-        if (a1 && k1 < K) put(T, k1, x1, y1, z1);
+        if (a1 && k1 < K) put(T, k1, c1);
       }
       if (needy) {  // what my group found for me
         const unsigned long long gm = group_mask(rank);
@@ -1352,13 +1418,39 @@ __device__ __forceinline__ void draw_targets_wave(uint64_t seed, uint64_t env0, 
     }
     M = __ballot(cnt < K);
   }
-  for (; cnt < K; ++cnt) put(lane, cnt, 0.f, 0.f, 0.5f * radius);  // unreachable in practice, as in draw_targets
+  for (; cnt < K; ++cnt) put(lane, cnt, kFallbackTargetCode);  // unreachable in practice, as in draw_targets
   __builtin_amdgcn_wave_barrier();  // a lane's column was written by other lanes of its wave
+}
+
+// A thread's LDS column of draw_targets_wave ([2K][kBlock] codes) turned into the [3K][kBlock] floats in place: last target
+// first, so the rows written for target k (3k .. 3k + 2) lie past the code rows of every target below it (<= 2k - 1).
+__device__ __forceinline__ void decode_column(float* col, int K, float radius) {
+  for (int k = K - 1; k >= 0; --k) {
+    const TargetCode c = staged_code(col + 2 * k * kBlock, kBlock);
+    float x, y, z;
+    decode_target(c, radius, x, y, z);
+    col[3 * k * kBlock] = x;
+    col[(3 * k + 1) * kBlock] = y;
+    col[(3 * k + 2) * kBlock] = z;
+  }
+}
+
+// Target k of env i as a reset leaves it: the floats decoded from its code (MT_F_POINTS), and the code.
+__device__ __forceinline__ void store_target(const StepArgs& a, int64_t ld, uint32_t i, int k, TargetCode c, float radius) {
+  float x, y, z;
+  decode_target(c, radius, x, y, z);
+  float* row = a.points + (int64_t)(3 * k) * ld;
+  row[i] = x;
+  (row + ld)[i] = y;
+  (row + 2 * ld)[i] = z;
+  uint32_t* crow = a.codes + (int64_t)(2 * k) * ld;
+  crow[i] = c.lo;
+  (crow + ld)[i] = c.hi;
 }
 
 // The draw of an env that is spread over L lanes of a wave (lane = q * (64 / L) + e: reset_split_kernel, rollout_split_kernel):
 // sub-lane q evaluates blocks q, q + L, q + 2 L, ...; in every round the accepted candidates are numbered in block order across
-// the env's sub-lanes (their counts travel by shuffle), so the K targets handed to `put(k, x, y, z)` -- by whichever sub-lane
+// the env's sub-lanes (their counts travel by shuffle), so the K target codes handed to `put(k, code)` -- by whichever sub-lane
 // found them -- are exactly the first K accepted candidates of draw_targets' sequential order: the same bits.  Every sub-lane of
 // the env must call it (`go` = the env wants targets; equal in all of them, so they leave the loop together).
 template <int L, class Put>
@@ -1369,8 +1461,9 @@ __device__ __forceinline__ void draw_targets_split(uint64_t seed, uint64_t env_i
   for (uint32_t round = 0; round < 2048u / L && cnt < K; ++round) {
     const u32x4 w = stream_block(seed, env_id, kTagTarget, episode, round * L + q);
     float x0, y0, z0, x1, y1, z1;
-    const bool a0 = target_candidate<0>(w, radius, x0, y0, z0);
-    const bool a1 = target_candidate<1>(w, radius, x1, y1, z1);
+    TargetCode c0, c1;
+    const bool a0 = target_candidate<0>(w, radius, x0, y0, z0, &c0);
+    const bool a1 = target_candidate<1>(w, radius, x1, y1, z1, &c1);
     const int mine = (a0 ? 1 : 0) + (a1 ? 1 : 0);
     int before = 0, total = 0;
 #pragma unroll
@@ -1380,13 +1473,13 @@ __device__ __forceinline__ void draw_targets_split(uint64_t seed, uint64_t env_i
       before += (qq < (int)q) ? c : 0;
     }
     const int k0 = cnt + before;
-    if (a0 && k0 < K) put(k0, x0, y0, z0);
+    if (a0 && k0 < K) put(k0, c0);
     const int k1 = k0 + (a0 ? 1 : 0);
-    if (a1 && k1 < K) put(k1, x1, y1, z1);
+    if (a1 && k1 < K) put(k1, c1);
     cnt += total;
   }
   if (q == 0)
-    for (; cnt < K; ++cnt) put(cnt, 0.f, 0.f, 0.5f * radius);  // unreachable in practice, as in draw_targets
+    for (; cnt < K; ++cnt) put(cnt, kFallbackTargetCode);  // unreachable in practice, as in draw_targets
 }
 
 template <int D, bool RANDOM, bool ONLY_DONE>
@@ -1446,8 +1539,8 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(const StepArgs a, float r
     // manytor.py:229-239: uniform in the cube, keep z >= 0 and |p| <= radius.  z is drawn from
     // [0, R) directly (same conditional law).  fp32, one rounding per op, mirrored by oracle/philox_ref.py.
     // Envs of one wave accept their k-th target at different candidates, so storing from inside the draw loop
-    // would write partial lines of different rows per instruction.  The accepted targets are parked in the env's
-    // LDS column ([3K][kBlock] floats, conflict-free) and written out row by row afterwards.
+    // would write partial lines of different rows per instruction.  The codes of the accepted targets are parked in the
+    // env's LDS column ([2K][kBlock] words, conflict-free) and written out row by row afterwards, codes and floats.
     extern __shared__ float stage[];
     __shared__ uint8_t slots[kBlock / 64][64];
     const uint32_t lane = threadIdx.x & 63u;
@@ -1456,7 +1549,7 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(const StepArgs a, float r
                       slots[threadIdx.x >> 6]);
     if (go) {
       const float* col = stage + threadIdx.x;
-      for (int r = 0; r < 3 * a.K; ++r) (a.points + (int64_t)r * ld)[i] = col[r * kBlock];
+      for (int k = 0; k < a.K; ++k) store_target(a, ld, i, k, staged_code(col + 2 * k * kBlock, kBlock), radius);
     }
   }
   if (valid && (threadIdx.x & 63) == 0) a.done_bits[i >> 6] = 0ull;  // every env of the wave has done == 0 now
@@ -1467,12 +1560,12 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(const StepArgs a, float r
 // launch and the stores are about half).  Lane layout as in step_split_kernel (lane = q * (64 / L) + e).  Sub-lane q of an
 // env evaluates blocks q, q + L, q + 2 L, ...; in every round the accepted candidates are numbered in block order
 // across the env's sub-lanes (their counts travel by shuffle), so the K targets are exactly the first K accepted
-// candidates of draw_targets' sequential order: the same bits as reset_kernel.  The targets are parked in the env's
-// LDS column ([3K][kBlock / L]) and written out by the sub-lanes in turn; everything else is done by sub-lane 0.
+// candidates of draw_targets' sequential order: the same bits as reset_kernel.  The target codes are parked in the env's
+// LDS column ([2K][kBlock / L]) and written out (codes and floats) by the sub-lanes in turn; everything else by sub-lane 0.
 template <int D, bool ONLY_DONE, int L>
 __global__ __launch_bounds__(kBlock) void reset_split_kernel(const StepArgs a, float radius) {
   static_assert(L == 2 || L == 4, "an env is spread over 2 or 4 lanes");
-  extern __shared__ float stage[];  // [3K][kBlock / L]
+  extern __shared__ float stage[];  // [2K][kBlock / L] target codes
   constexpr int EPW = 64 / L;
   constexpr int EPB = kBlock / L;
   const uint32_t lane = threadIdx.x & 63u;
@@ -1495,16 +1588,15 @@ __global__ __launch_bounds__(kBlock) void reset_split_kernel(const StepArgs a, f
   const uint64_t seed = ((uint64_t)a.seed_hi << 32) | a.seed_lo;
   const uint64_t env_id = (uint64_t)(a.env_base + i);
   const int K = a.K;
-  auto put = [&](int k, float x, float y, float z) {
-    float* cell = col + 3 * k * EPB;
-    cell[0] = x;
-    cell[EPB] = y;
-    cell[2 * EPB] = z;
+  auto put = [&](int k, TargetCode c) {  // (bit patterns in the float stage, as in draw_targets_wave)
+    float* cell = col + 2 * k * EPB;
+    cell[0] = __uint_as_float(c.lo);
+    cell[EPB] = __uint_as_float(c.hi);
   };
   draw_targets_split<L>(seed, env_id, episode, go, K, radius, q, e, put);
   __builtin_amdgcn_wave_barrier();  // the columns were written by the env's sub-lanes; a wave only touches its own
   if (live && go)
-    for (int r = (int)q; r < 3 * K; r += L) (a.points + (int64_t)r * ld)[i] = col[r * EPB];
+    for (int k = (int)q; k < K; k += L) store_target(a, ld, i, k, staged_code(col + 2 * k * EPB, EPB), radius);
   if (live && q == 0) {
     if (ONLY_DONE && dn == 2) a.done[i] = 0;
     if (go) {
@@ -1613,6 +1705,7 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(const StepArgs a, const
     const uint32_t lane = threadIdx.x & 63u;
     draw_targets_wave(((uint64_t)r.reset_seed_hi << 32) | r.reset_seed_lo, (uint64_t)(a.env_base + (i - lane)), episode, mine, a.K, r.radius,
                       tile + (threadIdx.x - lane), draw_slots[threadIdx.x >> 6]);
+    decode_column(col, a.K, r.radius);
     if (!(kTable && RPF) && !mine) return;
   } else if (RPF) {
 #pragma unroll
@@ -1785,11 +1878,9 @@ __global__ __launch_bounds__(kBlock) void rollout_split_kernel(const StepArgs a,
     if (live && q == 0) a.last_return[i] = total;
     total = 0.f;
     draw_targets_split<L>(((uint64_t)r.reset_seed_hi << 32) | r.reset_seed_lo, env_id, episode, true, a.K, r.radius, q, lane % EPW,
-                          [&](int k, float x, float y, float z) {
+                          [&](int k, TargetCode c) {
                             float* pk = col + 3 * k * EPB;
-                            pk[0] = x;
-                            pk[EPB] = y;
-                            pk[2 * EPB] = z;
+                            decode_target(c, r.radius, pk[0], pk[EPB], pk[2 * EPB]);
                           });
     __builtin_amdgcn_wave_barrier();  // a target's cells may have been written by another sub-lane of the env (same wave)
   } else if (RPF) {  // this sub-lane's first targets into registers (target index p = q + L * m)

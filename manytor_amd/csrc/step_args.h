@@ -30,6 +30,7 @@ struct StepArgs {
   float* actions;                 // [D][ld]
   float* goals;                   // [D][ld]
   float* points;                  // [3K][ld]
+  uint32_t* codes;                // [2K][ld] the targets as their draw codes (kernels.h TargetCode); internal, valid while the host says so
   uint32_t* alive;                // [ld] bit p = target p alive
   float* total_reward;            // [ld]
   float* obs;                     // [3K][ld]
@@ -44,7 +45,7 @@ struct StepArgs {
   const float* trig_table;        // [450][2] (sin, cos) of the whole degrees -270 .. 179, filled once at mt_create (kernels.h: SinCos)
   float* zmin;                    // [ld] MT_FLAG_DEBUG_ZMIN only (else NULL): the z-minimum the ground test of the last step used
   // the first step launch of an episode (step_kernel<.., FRESH>): the deferred full reset it starts with -- the seed and
-  // the episode index of the target stream, the radius of the half ball
+  // the episode index of the target stream; the radius of the half ball (the handle's, also what decodes target codes)
   uint32_t reset_seed_lo, reset_seed_hi, reset_episode;
   float radius;
   float* snap;                    // [n] NULL, or (the last step launch of an mt_rollout) the overlapped gather's snapshot row: the returns again
