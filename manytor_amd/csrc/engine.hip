@@ -12,7 +12,9 @@
 #include <cstring>
 #include <mutex>
 #include <new>
+#include <iterator>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "engine_internal.h"
@@ -179,7 +181,7 @@ static const DispatchPolicy kPolicy{};
 // launch time the usual way, with dynamic LDS nobody touches: a block then claims 1 / cap of the CU's 160 KB.
 // MT_BLOCKS_PER_CU overrides (0 = none; 1 and 2 cannot be realised inside the default 64 KB dynamic-LDS limit and are
 // raised to 3).
-static int step_blocks_per_cu(mt_handle h, int64_t n_launch) {
+static int step_blocks_per_cu(const mt_engine* h, int64_t n_launch) {
   if (h->blocks_per_cu_override >= 0) return h->blocks_per_cu_override;
   if (n_launch >= h->n) return 0;  // chain launches only
   for (const BlockCap& c : kPolicy.block_caps)
@@ -193,7 +195,7 @@ static size_t lds_pad_for_blocks(int blocks_per_cu, size_t static_lds) {
 }
 
 // Envs per chain: equal shares rounded up to whole 256-env blocks; the last chain takes what is left (possibly less).
-int64_t chain_span(mt_handle h, int chains) {
+int64_t chain_span(const mt_engine* h, int chains) {
   const int64_t per = (h->n + chains - 1) / chains;
   return (per + 255) / 256 * 256;
 }
@@ -229,20 +231,14 @@ static void choose_dispatch(mt_handle h) {
   h->static_kind = ((cfg->flags & (MT_FLAG_NO_SPECIALIZE | MT_FLAG_DH_IN_LDS)) || h->custom_frames) ? 0 : match_static(h->args.dh, h->D);
 
   // ---- one launch per step: which step kernel for which batch (all variants give the same bits) ----
-  h->split = n <= P.step_split4_max ? 4 : (n <= P.step_split2_max ? 2 : 0);
-  h->prefetch = h->static_kind == 1 || n <= P.prefetch_other_max;
-  h->rollout_split = n <= P.fused_split4_max ? 4 : (n <= P.fused_split2_max ? 2 : 0);
-  bool split_forced = false;
+  // (the schedules themselves are filled at the end, once the chain count is known: schedule_for)
+  int forced_lanes = 0, forced_prefetch = -1;  // MT_SPLIT (step and rollout kernels alike) / MT_PREFETCH, for every scope
   if (env_int("MT_SPLIT", &v)) {
-    h->split = (v == 2 || v == 4) ? (int)v : 0;
-    h->rollout_split = h->split;
-    split_forced = true;
+    forced_lanes = (v == 2 || v == 4) ? (int)v : 1;
     seen("MT_SPLIT");
   }
-  h->prefetch_forced = false;
   if (env_int("MT_PREFETCH", &v)) {
-    h->prefetch = v != 0;
-    h->prefetch_forced = true;
+    forced_prefetch = v != 0;
     seen("MT_PREFETCH");
   }
   h->reset_split = n <= P.reset_split_max;
@@ -328,158 +324,23 @@ static void choose_dispatch(mt_handle h) {
     seen("MT_ROLLOUT_EARLY");
   }
 
-  if (h->custom_frames) {
-    h->lds_table = false;
-    h->split = 0;
-    h->rollout_split = 0;
-    h->prefetch = false;
-  }
+  if (h->custom_frames) h->lds_table = false;
+  // The schedule of launches over `envs` envs, against the thresholds of their scope
+  auto schedule_for = [&](int64_t envs, int64_t split4_max, int64_t split2_max, int64_t prefetch_other_max) {
+    mt_engine::Schedule s;
+    s.step_lanes = envs <= split4_max ? 4 : (envs <= split2_max ? 2 : 1);
+    s.prefetch = h->static_kind == 1 || envs <= prefetch_other_max;
+    s.rollout_lanes = envs <= P.fused_split4_max ? 4 : (envs <= P.fused_split2_max ? 2 : 1);
+    if (forced_lanes) s.step_lanes = s.rollout_lanes = forced_lanes;
+    if (forced_prefetch >= 0) s.prefetch = forced_prefetch != 0;
+    if (h->custom_frames) s = mt_engine::Schedule{};  // RtTableF kernels: one env per lane, no prefetch
+    return s;
+  };
+  h->sched[mt_engine::kBatch] = schedule_for(n, P.step_split4_max, P.step_split2_max, P.prefetch_other_max);
   // A chain of a multi-chain call is a batch of chain_span() envs: its launches use the schedule for THAT size
-  h->chain_split = h->split;
-  h->chain_prefetch = h->prefetch;
-  h->chain_rollout_split = h->rollout_split;
-  if (h->chains > 1) {
-    const int64_t span = chain_span(h, h->chains);
-    h->chain_split = span <= P.chain_split4_max ? 4 : (span <= P.chain_split2_max ? 2 : 0);
-    h->chain_prefetch = h->static_kind == 1 || span <= P.chain_prefetch_other_max;
-    h->chain_rollout_split = span <= P.fused_split4_max ? 4 : (span <= P.fused_split2_max ? 2 : 0);
-    if (split_forced) h->chain_split = h->chain_rollout_split = h->split;
-    if (h->prefetch_forced) h->chain_prefetch = h->prefetch;
-    if (h->custom_frames) {
-      h->chain_split = 0;
-      h->chain_rollout_split = 0;
-      h->chain_prefetch = false;
-    }
-  }
-}
-
-// whole_rows: the launch covers the batch or a 256-aligned range of it (not the single-env view), so threads past the
-// end of the range may read on to the end of their block inside the rows (what the TT kernels do before their barrier)
-// codes: the handle's target codes are valid (engine_internal.h, codes_valid); h->codes_valid is left true only where the
-// launch reads (and so keeps) them
-template <class Tbl, bool LDS_OK>
-void launch_step_t(mt_handle h, const StepArgs& args, bool sample, bool whole_rows, bool codes) {
-  const dim3 g = grid_for(args.n), b(kBlock);
-#define MT_LAUNCH_STEP(SAMPLE_, TRIG_, LDS_) \
-  hipLaunchKernelGGL((step_kernel<Tbl, SAMPLE_, TRIG_, LDS_>), g, b, 0, h->stream, args)
-  if (LDS_OK && h->lds_table) {
-    if constexpr (LDS_OK) {
-      if (sample) MT_LAUNCH_STEP(true, 0, true); else MT_LAUNCH_STEP(false, 0, true);
-    }
-    return;
-  }
-  // sampled actions of a compile-time table on the whole batch: both end poses' sines / cosines from the table (TT)
-  bool tt = false;
-  if constexpr (ActionTrigTable<Tbl>::value) tt = sample && h->trig == 0 && h->trig_steps && whole_rows;
-  if (h->trig == 0 && h->split) {  // tiny batches: one env over 2 or 4 lanes (kernels.h, step_split_kernel)
-    const int64_t per_block = kBlock / h->split;
-    const dim3 gs((unsigned)((args.n + per_block - 1) / per_block));
-    if constexpr (ActionTrigTable<Tbl>::value) {
-      if (tt) {
-        if (h->split == 2)
-          hipLaunchKernelGGL((step_split_kernel<Tbl, true, 2, true>), gs, b, 0, h->stream, args);
-        else
-          hipLaunchKernelGGL((step_split_kernel<Tbl, true, 4, true>), gs, b, 0, h->stream, args);
-        return;
-      }
-    }
-    if (h->split == 2) {
-      if (sample)
-        hipLaunchKernelGGL((step_split_kernel<Tbl, true, 2>), gs, b, 0, h->stream, args);
-      else
-        hipLaunchKernelGGL((step_split_kernel<Tbl, false, 2>), gs, b, 0, h->stream, args);
-    } else {
-      if (sample)
-        hipLaunchKernelGGL((step_split_kernel<Tbl, true, 4>), gs, b, 0, h->stream, args);
-      else
-        hipLaunchKernelGGL((step_split_kernel<Tbl, false, 4>), gs, b, 0, h->stream, args);
-    }
-    return;
-  }
-  if constexpr (ActionTrigTable<Tbl>::value) {
-    if (tt) {
-      const size_t pad = h->prefetch ? lds_pad_for_blocks(step_blocks_per_cu(h, args.n), kTrigEntries * sizeof(SinCos)) : 0;
-      // the prefetch kernels read the targets as their codes while those are valid (kernels.h, CODES: 28 B per env less)
-      if (h->prefetch && codes) {
-        if (args.n >= h->flat_from)
-          hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, true, true, false, true>), g, b, pad, h->stream, args);
-        else
-          hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, true, false, false, true>), g, b, pad, h->stream, args);
-        h->codes_valid = true;
-      } else if (h->prefetch && args.n >= h->flat_from)  // HBM-bound launches: kernels.h, LaneOffset<false>; see step_blocks_per_cu
-        hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, true, true>), g, b, pad, h->stream, args);
-      else if (h->prefetch)
-        hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, true>), g, b, pad, h->stream, args);
-      else
-        hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, 0, true>), g, b, 0, h->stream, args);
-      return;
-    }
-  }
-  if (h->trig == 0 && h->prefetch) {  // target loads in flight before the kinematics (kernels.h, PF)
-    if (args.n >= h->flat_from) {
-      if (sample)
-        hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, false, true>), g, b, 0, h->stream, args);
-      else
-        hipLaunchKernelGGL((step_kernel<Tbl, false, 0, false, kPrefetch, false, true>), g, b, 0, h->stream, args);
-    } else if (sample) {
-      hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch>), g, b, 0, h->stream, args);
-    } else {
-      hipLaunchKernelGGL((step_kernel<Tbl, false, 0, false, kPrefetch>), g, b, 0, h->stream, args);
-    }
-    return;
-  }
-  switch (h->trig) {
-    case 1: if (sample) MT_LAUNCH_STEP(true, 1, false); else MT_LAUNCH_STEP(false, 1, false); break;
-    case 2: if (sample) MT_LAUNCH_STEP(true, 2, false); else MT_LAUNCH_STEP(false, 2, false); break;
-    case 3: if (sample) MT_LAUNCH_STEP(true, 3, false); else MT_LAUNCH_STEP(false, 3, false); break;
-    case 4: if (sample) MT_LAUNCH_STEP(true, 4, false); else MT_LAUNCH_STEP(false, 4, false); break;
-    case 5: if (sample) MT_LAUNCH_STEP(true, 5, false); else MT_LAUNCH_STEP(false, 5, false); break;
-    default: if (sample) MT_LAUNCH_STEP(true, 0, false); else MT_LAUNCH_STEP(false, 0, false); break;
-  }
-#undef MT_LAUNCH_STEP
-}
-
-// The first step of an episode with the deferred reset as the step kernel's own prologue (kernels.h, FRESH): the sampled-
-// action kernels of the static tables, one env per lane.  false = no such kernel for this handle's schedule (the caller
-// falls back to one step of the rollout kernel).  `args` carries reset_seed / reset_episode / radius.
-template <class Tbl>
-bool launch_step_fresh_t(mt_handle h, const StepArgs& args) {
-  if constexpr (!ActionTrigTable<Tbl>::value) {
-    return false;
-  } else {
-    if (h->trig != 0 || !h->trig_steps || h->split || h->lds_table || h->trace) return false;
-    const size_t stage = (size_t)2 * args.K * kBlock * sizeof(float), fixed = kTrigEntries * sizeof(SinCos) + 512;
-    if (stage + fixed > 65536) return false;  // (K > 20: above the default dynamic-LDS limit)
-    const dim3 g = grid_for(args.n), b(kBlock);
-    const size_t lds = std::max(stage, h->prefetch ? lds_pad_for_blocks(step_blocks_per_cu(h, args.n), fixed) : (size_t)0);
-    h->codes_valid = false;  // the drawn targets are written as floats only
-    if (h->prefetch && args.n >= h->flat_from)
-      hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, true, true, true>), g, b, lds, h->stream, args);
-    else if (h->prefetch)
-      hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, kPrefetch, true, false, true>), g, b, lds, h->stream, args);
-    else
-      hipLaunchKernelGGL((step_kernel<Tbl, true, 0, false, 0, true, false, true>), g, b, lds, h->stream, args);
-    return true;
-  }
-}
-bool launch_step_fresh(mt_handle h, const StepArgs& args) {
-  if (h->custom_frames) return false;
-  if (h->static_kind == 1) return launch_step_fresh_t<Ref4Table>(h, args);
-  if (h->static_kind == 2) return launch_step_fresh_t<Dh7Table>(h, args);
-  return false;
-}
-
-template <int D>
-void launch_step_d(mt_handle h, const StepArgs& args, bool sample, bool whole_rows) {
-  launch_step_t<RtTable<D>, true>(h, args, sample, whole_rows, false);
-}
-
-template <int D>
-void launch_trace_d(mt_handle h, const StepArgs& args, float* trace, bool sample) {
-  if (sample)
-    hipLaunchKernelGGL((trace_kernel<D, true>), grid_for(args.n), dim3(kBlock), 0, h->stream, args, trace);
-  else
-    hipLaunchKernelGGL((trace_kernel<D, false>), grid_for(args.n), dim3(kBlock), 0, h->stream, args, trace);
+  h->sched[mt_engine::kChain] =
+      h->chains > 1 ? schedule_for(chain_span(h, h->chains), P.chain_split4_max, P.chain_split2_max, P.chain_prefetch_other_max)
+                    : h->sched[mt_engine::kBatch];
 }
 
 #define MT_DISPATCH_D(D_, FN, ...)   \
@@ -494,38 +355,200 @@ void launch_trace_d(mt_handle h, const StepArgs& args, float* trace, bool sample
     default: break;                  \
   }
 
-template <int D>
-void launch_step_frames_d(mt_handle h, const StepArgs& args, bool sample) {
-  const dim3 g = grid_for(args.n), b(kBlock);
-  if (h->trig == 1) {  // long routes (mt_create: more than 12 rotations per half) or MT_FLAG_DIRECT_TRIG
-    if (sample)
-      hipLaunchKernelGGL((step_kernel<RtTableF<D>, true, 1, false, 0>), g, b, 0, h->stream, args);
-    else
-      hipLaunchKernelGGL((step_kernel<RtTableF<D>, false, 1, false, 0>), g, b, 0, h->stream, args);
-    return;
+// ---- what one step launch is: resolved once (plan_step), launched in one place (launch_plan), reported from the same value --
+// The template arguments of step_kernel / step_split_kernel (kernels.h) by name; SAMPLE is apart (StepPlan::sample).
+struct StepVariant {
+  int trig = 0;        // TRIG
+  bool lds = false;    // LDS: the DH table in LDS (runtime tables, recurrence only)
+  int lanes = 1;       // 1: step_kernel; 2 / 4: step_split_kernel<.., L>
+  int pf = 0;          // PF
+  bool tt = false;     // TT
+  bool flat = false;   // FLAT
+  bool fresh = false;  // FRESH
+  bool codes = false;  // CODES
+};
+constexpr unsigned variant_key(const StepVariant& v) {
+  return (unsigned)v.trig | (unsigned)v.lds << 3 | (unsigned)v.lanes << 4 | (unsigned)(v.pf != 0) << 7 | (unsigned)v.tt << 8 |
+         (unsigned)v.flat << 9 | (unsigned)v.fresh << 10 | (unsigned)v.codes << 11;
+}
+
+// Every instantiation the library holds, per table type.  A row without TT exists for sampled and for staged actions
+// (SAMPLE = true / false), a row with TT for sampled actions only.  launch_plan instantiates these rows and nothing else.
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Wc++20-designator"
+constexpr StepVariant kRuntimeVariants[] = {  // RtTable<D>
+    {.trig = 0}, {.trig = 1}, {.trig = 2}, {.trig = 3}, {.trig = 4}, {.trig = 5},
+    {.lds = true},
+    {.lanes = 2}, {.lanes = 4},
+    {.pf = kPrefetch}, {.pf = kPrefetch, .flat = true},
+};
+constexpr StepVariant kFramesVariants[] = {{.trig = 0}, {.trig = 1}};  // RtTableF<D>
+constexpr StepVariant kStaticVariants[] = {  // Ref4Table, Dh7Table
+    {.trig = 0}, {.trig = 1}, {.trig = 2}, {.trig = 3}, {.trig = 4}, {.trig = 5},
+    {.lanes = 2}, {.lanes = 4},
+    {.lanes = 2, .tt = true}, {.lanes = 4, .tt = true},
+    {.pf = kPrefetch}, {.pf = kPrefetch, .flat = true},
+    {.pf = 0, .tt = true}, {.pf = kPrefetch, .tt = true}, {.pf = kPrefetch, .tt = true, .flat = true},
+    {.pf = kPrefetch, .tt = true, .codes = true}, {.pf = kPrefetch, .tt = true, .flat = true, .codes = true},
+    {.pf = 0, .tt = true, .fresh = true}, {.pf = kPrefetch, .tt = true, .fresh = true},
+    {.pf = kPrefetch, .tt = true, .flat = true, .fresh = true},
+};
+#pragma clang diagnostic pop
+
+enum class TableKind { kRuntime = 0, kRef4 = 1, kDh7 = 2, kFrames = 3 };  // RtTable<D>, Ref4Table, Dh7Table, RtTableF<D>
+struct StepPlan {
+  TableKind table = TableKind::kRuntime;
+  int D = 0;
+  bool sample = false;  // SAMPLE: actions drawn in the kernel (false: staged actions)
+  StepVariant v;
+  int blocks_per_cu = 0;  // resident-blocks cap (0 = none) ...
+  size_t lds_bytes = 0;   // ... and the dynamic LDS that realises it (FRESH: at least the staging columns of the draw)
+  dim3 grid;
+  bool exists = true;  // false: no such kernel for this handle's schedule (FRESH only)
+};
+
+// THE rules of which step kernel a launch of `n` envs gets -- every variant gives the same bits, so this is about time only:
+//   scope  whose schedule: the whole batch, one chain's 256-aligned range of it, or the single-env view (batch schedule).
+//          Batch and chain launches cover whole rows, so threads past the end of the range may read on to the end of their
+//          block inside the rows (what the TT kernels do before their barrier); the single-env view does not
+//   codes  the handle's target codes are valid (engine_internal.h, codes_valid)
+//   fresh  the first step of an episode with the deferred reset as the step kernel's own prologue (kernels.h, FRESH): the
+//          sampled-action kernels of the static tables, one env per lane.  exists = false: the caller falls back to one
+//          step of the rollout kernel
+// Cheap enough to run per launch: no allocation, no strings.
+StepPlan plan_step(const mt_engine* h, mt_engine::Scope scope, int64_t n, bool sample, bool codes, bool fresh = false) {
+  const mt_engine::Schedule& s = h->sched[scope == mt_engine::kChain ? mt_engine::kChain : mt_engine::kBatch];
+  const bool whole_rows = scope != mt_engine::kOneEnv;
+  StepPlan p;
+  p.table = h->custom_frames ? TableKind::kFrames : (TableKind)h->static_kind;
+  p.D = h->D;
+  p.sample = sample;
+  p.grid = grid_for(n);
+  StepVariant& v = p.v;
+  if (fresh) {
+    const size_t stage = (size_t)2 * h->K * kBlock * sizeof(float), fixed = kTrigEntries * sizeof(SinCos) + 512;
+    p.exists = h->trig == 0 && h->trig_steps && s.step_lanes == 1 && !h->lds_table && !h->trace &&
+               stage + fixed <= 65536;  // (K > 20: above the default dynamic-LDS limit)
+    if (!p.exists) return p;
+    p.sample = true;
+    v.tt = v.fresh = true;
+    v.pf = s.prefetch ? kPrefetch : 0;
+    v.flat = v.pf && n >= h->flat_from;
+    p.blocks_per_cu = v.pf ? step_blocks_per_cu(h, n) : 0;
+    p.lds_bytes = std::max(stage, lds_pad_for_blocks(p.blocks_per_cu, fixed));
+    return p;
   }
-  if (sample)
-    hipLaunchKernelGGL((step_kernel<RtTableF<D>, true, 0, false, 0>), g, b, 0, h->stream, args);
+  if (p.table == TableKind::kFrames) {  // runtime frames: the recurrence, or the polynomial sincos of long routes
+    v.trig = h->trig == 1 ? 1 : 0;      // (mt_create: more than 12 rotations per half) and MT_FLAG_DIRECT_TRIG
+    return p;
+  }
+  if (h->lds_table) {  // runtime tables only; the LDS-table kernel is the recurrence whatever the handle's trig says
+    v.lds = true;
+    return p;
+  }
+  if (h->trig != 0) {  // no schedules beside the recurrence
+    v.trig = h->trig;
+    return p;
+  }
+  // sampled actions of a compile-time table on whole rows: both end poses' sines / cosines from the table (TT)
+  v.tt = sample && h->trig_steps && whole_rows;
+  if (s.step_lanes > 1) {  // tiny batches: one env over 2 or 4 lanes (kernels.h, step_split_kernel)
+    v.lanes = s.step_lanes;
+    const int64_t per_block = kBlock / v.lanes;
+    p.grid = dim3((unsigned)((n + per_block - 1) / per_block));
+    return p;
+  }
+  v.pf = s.prefetch ? kPrefetch : 0;    // target loads in flight before the kinematics (kernels.h, PF)
+  v.flat = v.pf && n >= h->flat_from;   // HBM-bound launches: kernels.h, LaneOffset<false>
+  // the prefetch kernels read the targets as their codes while those are valid (kernels.h, CODES: 28 B per env less)
+  v.codes = v.pf && v.tt && codes;
+  if (v.pf && v.tt) {  // see step_blocks_per_cu
+    p.blocks_per_cu = step_blocks_per_cu(h, n);
+    p.lds_bytes = lds_pad_for_blocks(p.blocks_per_cu, kTrigEntries * sizeof(SinCos));
+  }
+  return p;
+}
+
+// The only place that spells the kernels' template argument lists: row I of ROWS, every argument by its name.
+template <class Tbl, bool SAMPLE, const auto& ROWS, size_t I>
+void launch_variant(const StepPlan& p, hipStream_t stream, const StepArgs& args) {
+  constexpr StepVariant V = ROWS[I];
+  if constexpr (V.lanes > 1)
+    hipLaunchKernelGGL((step_split_kernel<Tbl, SAMPLE, V.lanes, V.tt>), p.grid, dim3(kBlock), p.lds_bytes, stream, args);
   else
-    hipLaunchKernelGGL((step_kernel<RtTableF<D>, false, 0, false, 0>), g, b, 0, h->stream, args);
+    hipLaunchKernelGGL((step_kernel<Tbl, SAMPLE, V.trig, V.lds, V.pf, V.tt, V.flat, V.fresh, V.codes>), p.grid, dim3(kBlock),
+                       p.lds_bytes, stream, args);
+}
+// ... if row I is the plan's variant (false: it is not)
+template <class Tbl, const auto& ROWS, size_t I>
+bool launch_row(const StepPlan& p, hipStream_t stream, const StepArgs& args) {
+  if (variant_key(p.v) != variant_key(ROWS[I])) return false;
+  if (p.sample)
+    launch_variant<Tbl, true, ROWS, I>(p, stream, args);
+  else if constexpr (!ROWS[I].tt)
+    launch_variant<Tbl, false, ROWS, I>(p, stream, args);
+  else
+    return false;  // TT serves sampled actions only
+  return true;
+}
+template <class Tbl, const auto& ROWS, size_t... I>
+bool launch_rows(const StepPlan& p, hipStream_t stream, const StepArgs& args, std::index_sequence<I...>) {
+  return (launch_row<Tbl, ROWS, I>(p, stream, args) || ...);
+}
+template <class Tbl, const auto& ROWS>
+bool launch_table(const StepPlan& p, hipStream_t stream, const StepArgs& args) {
+  return launch_rows<Tbl, ROWS>(p, stream, args, std::make_index_sequence<std::size(ROWS)>{});
+}
+template <int D>
+void launch_plan_d(const StepPlan& p, hipStream_t stream, const StepArgs& args, bool* launched) {
+  *launched = p.table == TableKind::kFrames ? launch_table<RtTableF<D>, kFramesVariants>(p, stream, args)
+                                            : launch_table<RtTable<D>, kRuntimeVariants>(p, stream, args);
 }
 
-// One env step of the envs `args` describes (the whole batch, or one env of it: args_for_env); `trace` is the
-// matching view of the sub-step trace buffer or NULL.
-void launch_step(mt_handle h, const StepArgs& args, float* trace, bool sample, bool whole_rows) {
-  if (trace) MT_DISPATCH_D(h->D, launch_trace_d, h, args, trace, sample);  // first: it needs the previous pose
-  const bool codes = h->codes_valid;
-  h->codes_valid = false;  // every step kernel may zero targets; only the ones that read codes zero those too
-  if (h->custom_frames) {
-    MT_DISPATCH_D(h->D, launch_step_frames_d, h, args, sample);
-    return;
+// Launches the kernel a plan names.  A plan outside the tables above is a bug in plan_step, not a condition to run past.
+void launch_plan(const StepPlan& p, hipStream_t stream, const StepArgs& args) {
+  bool launched = false;
+  if (p.table == TableKind::kRef4)
+    launched = launch_table<Ref4Table, kStaticVariants>(p, stream, args);
+  else if (p.table == TableKind::kDh7)
+    launched = launch_table<Dh7Table, kStaticVariants>(p, stream, args);
+  else
+    MT_DISPATCH_D(p.D, launch_plan_d, p, stream, args, &launched);
+  if (!launched) {
+    std::fprintf(stderr, "manytor: no step kernel for table %d, D %d, sample %d, variant key 0x%x\n", (int)p.table, p.D,
+                 (int)p.sample, variant_key(p.v));
+    std::abort();
   }
-  if (h->static_kind == 1) return launch_step_t<Ref4Table, false>(h, args, sample, whole_rows, codes);
-  if (h->static_kind == 2) return launch_step_t<Dh7Table, false>(h, args, sample, whole_rows, codes);
-  MT_DISPATCH_D(h->D, launch_step_d, h, args, sample, whole_rows);
 }
 
-void launch_step(mt_handle h, bool sample) { launch_step(h, h->args, h->trace, sample, true); }
+template <int D>
+void launch_trace_d(mt_handle h, const StepArgs& args, float* trace, bool sample) {
+  if (sample)
+    hipLaunchKernelGGL((trace_kernel<D, true>), grid_for(args.n), dim3(kBlock), 0, h->stream, args, trace);
+  else
+    hipLaunchKernelGGL((trace_kernel<D, false>), grid_for(args.n), dim3(kBlock), 0, h->stream, args, trace);
+}
+
+// One env step of the envs `args` describes (the whole batch, a chain's range, or one env of it: args_for_env), on the
+// schedule of `scope`; `trace` is the matching view of the sub-step trace buffer or NULL.
+void launch_step(mt_handle h, mt_engine::Scope scope, const StepArgs& args, float* trace, bool sample) {
+  if (trace) MT_DISPATCH_D(h->D, launch_trace_d, h, args, trace, sample);  // first: it needs the previous pose
+  const StepPlan p = plan_step(h, scope, args.n, sample, h->codes_valid);
+  launch_plan(p, h->stream, args);
+  h->codes_valid = p.v.codes;  // every step kernel may zero targets; only the ones that read codes zero those too
+}
+
+void launch_step(mt_handle h, bool sample) { launch_step(h, mt_engine::kBatch, h->args, h->trace, sample); }
+
+// The first step of an episode with the deferred reset inside it (plan_step, fresh); false = no such kernel for this
+// handle's schedule.  `args` carries reset_seed / reset_episode / radius.
+bool launch_step_fresh(mt_handle h, mt_engine::Scope scope, const StepArgs& args) {
+  const StepPlan p = plan_step(h, scope, args.n, true, false, true);
+  if (!p.exists) return false;
+  launch_plan(p, h->stream, args);
+  h->codes_valid = p.v.codes;  // (false: the drawn targets are written as floats only)
+  return true;
+}
 
 // ---- multi-chain rollouts ------------------------------------------------------------------------------------------
 StepArgs args_for_range(mt_handle h, const StepArgs& base, int64_t off, int64_t cnt);
@@ -546,16 +569,10 @@ void launch_chain(mt_handle h, const StepArgs& a0, uint32_t major0, int T, int c
   const int64_t span = chain_span(h, chains), off = (int64_t)c * span;
   if (off >= h->n) return;
   StepArgs as = args_for_range(h, a0, off, std::min(span, h->n - off));
-  const int keep_split = h->split;
-  const bool keep_pf = h->prefetch;
-  h->split = h->chain_split;
-  h->prefetch = h->chain_prefetch;
   for (int s = 0; s < T; ++s) {
     as.major = major0 + (uint32_t)s;
-    launch_step(h, as, nullptr, sample, true);
+    launch_step(h, mt_engine::kChain, as, nullptr, sample);
   }
-  h->split = keep_split;
-  h->prefetch = keep_pf;
 }
 
 // Chain c's FIRST step of an episode, the deferred reset inside it (launch_step_fresh); false: not served.
@@ -564,14 +581,7 @@ bool launch_chain_fresh(mt_handle h, const StepArgs& a0, uint32_t major, int cha
   if (off >= h->n) return true;
   StepArgs as = args_for_range(h, a0, off, std::min(span, h->n - off));
   as.major = major;
-  const int keep_split = h->split;
-  const bool keep_pf = h->prefetch;
-  h->split = h->chain_split;
-  h->prefetch = h->chain_prefetch;
-  const bool served = launch_step_fresh(h, as);
-  h->split = keep_split;
-  h->prefetch = keep_pf;
-  return served;
+  return launch_step_fresh(h, mt_engine::kChain, as);
 }
 
 // Chain c's stream (chain 0 runs on the handle's own stream).
@@ -594,35 +604,8 @@ int fork_chains(mt_handle h, int chains) {
 // them, any other call joins: MT_ENTER); on a caller's stream the call has to be complete in stream order when it returns.
 int settle_chains(mt_handle h) { return (h->lazy_chains && h->stream == h->own_stream) ? MT_OK : join_chains(h); }
 
-// The view of ONE env of the batch: every row base moved `env` elements to the right, n = 1.  The wavefront ballot
-// of such a launch goes to a spare word; the real done_bits word is rebuilt afterwards (done_bits_word_kernel).
-StepArgs args_for_env(mt_handle h, int64_t env) {
-  StepArgs a = h->args;
-  a.actions += env;
-  a.goals += env;
-  a.points += env;
-  a.codes += env;
-  a.alive += env;
-  a.total_reward += env;
-  a.obs += env;
-  a.reward += env;
-  a.done += env;
-  a.done_bits = h->spare_bits;
-  a.ee += env;
-  a.episodes += env;
-  a.last_return += env;
-  if (a.ring) a.ring += env;
-  if (a.zmin) a.zmin += env;
-  a.snap = nullptr;
-  a.n = 1;
-  a.env_base += env;
-  return a;
-}
-
-// The view of a contiguous RANGE of envs [off, off + cnt) of the batch, off a multiple of 256 (whole blocks, whole ballot
-// words, 1 KiB-aligned row segments): what one chain of a multi-chain mt_rollout launches on.
-StepArgs args_for_range(mt_handle h, const StepArgs& base, int64_t off, int64_t cnt) {
-  StepArgs a = base;
+// Every row base of `a` moved `off` envs to the right (done_bits, snap and n are the caller's: they differ per view).
+void shift_rows(StepArgs& a, int64_t off) {
   a.actions += off;
   a.goals += off;
   a.points += off;
@@ -632,15 +615,33 @@ StepArgs args_for_range(mt_handle h, const StepArgs& base, int64_t off, int64_t 
   a.obs += off;
   a.reward += off;
   a.done += off;
-  a.done_bits += off / 64;
   a.ee += off;
   a.episodes += off;
   a.last_return += off;
   if (a.ring) a.ring += off;
   if (a.zmin) a.zmin += off;
+  a.env_base += off;
+}
+
+// The view of ONE env of the batch, n = 1.  The wavefront ballot of such a launch goes to a spare word; the real
+// done_bits word is rebuilt afterwards (done_bits_word_kernel).
+StepArgs args_for_env(mt_handle h, int64_t env) {
+  StepArgs a = h->args;
+  shift_rows(a, env);
+  a.done_bits = h->spare_bits;
+  a.snap = nullptr;
+  a.n = 1;
+  return a;
+}
+
+// The view of a contiguous RANGE of envs [off, off + cnt) of the batch, off a multiple of 256 (whole blocks, whole ballot
+// words, 1 KiB-aligned row segments): what one chain of a multi-chain mt_rollout launches on.
+StepArgs args_for_range(mt_handle h, const StepArgs& base, int64_t off, int64_t cnt) {
+  StepArgs a = base;
+  shift_rows(a, off);
+  a.done_bits += off / 64;
   if (a.snap) a.snap += off;
   a.n = cnt;
-  a.env_base += off;
   return a;
 }
 
@@ -703,9 +704,9 @@ void launch_rollout_split_t(mt_handle h, const StepArgs& a, const RolloutArgs& r
 }
 
 template <class Tbl, int RPF>
-void launch_rollout_t(mt_handle h, const StepArgs& a, int split, const RolloutArgs& r) {
-  if (split == 4) return launch_rollout_split_t<Tbl, 4, RPF>(h, a, r);
-  if (split == 2) return launch_rollout_split_t<Tbl, 2, RPF>(h, a, r);
+void launch_rollout_t(mt_handle h, const StepArgs& a, int lanes, const RolloutArgs& r) {
+  if (lanes == 4) return launch_rollout_split_t<Tbl, 4, RPF>(h, a, r);
+  if (lanes == 2) return launch_rollout_split_t<Tbl, 2, RPF>(h, a, r);
   // 21.5 KB at K = 7, 96 KB at K = 32 (of 160 KB), + 3.6 KB for the action sin / cos table of the compile-time tables
   const size_t lds = (size_t)3 * h->K * kBlock * sizeof(float) + (ActionTrigTable<Tbl>::value ? kTrigEntries * sizeof(SinCos) : 0);
   if (lds > 65536)  // above the default dynamic-LDS limit the kernel has to be told
@@ -714,19 +715,16 @@ void launch_rollout_t(mt_handle h, const StepArgs& a, int split, const RolloutAr
   hipLaunchKernelGGL((rollout_kernel<Tbl, RPF>), grid_for(a.n), dim3(kBlock), lds, h->stream, a, r);
 }
 
-void launch_rollout(mt_handle h, const StepArgs& a, int split, const RolloutArgs& r, bool early = false) {
+template <int D>
+void launch_rollout_d(mt_handle h, const StepArgs& a, int lanes, const RolloutArgs& r) {
+  launch_rollout_t<RtTable<D>, 0>(h, a, lanes, r);
+}
+// `lanes` per env: the rollout_lanes of the launch's scope (engine_internal.h, Schedule), or 1
+void launch_rollout(mt_handle h, const StepArgs& a, int lanes, const RolloutArgs& r, bool early = false) {
   h->codes_valid = false;  // the rollout kernels write targets as floats only
-  if (h->static_kind == 1) return early ? launch_rollout_t<Ref4Table, kPrefetch>(h, a, split, r) : launch_rollout_t<Ref4Table, 0>(h, a, split, r);
-  if (h->static_kind == 2) return early ? launch_rollout_t<Dh7Table, kPrefetch>(h, a, split, r) : launch_rollout_t<Dh7Table, 0>(h, a, split, r);
-  switch (h->D) {
-    case 2: launch_rollout_t<RtTable<2>, 0>(h, a, split, r); break;
-    case 3: launch_rollout_t<RtTable<3>, 0>(h, a, split, r); break;
-    case 4: launch_rollout_t<RtTable<4>, 0>(h, a, split, r); break;
-    case 5: launch_rollout_t<RtTable<5>, 0>(h, a, split, r); break;
-    case 6: launch_rollout_t<RtTable<6>, 0>(h, a, split, r); break;
-    case 7: launch_rollout_t<RtTable<7>, 0>(h, a, split, r); break;
-    default: launch_rollout_t<RtTable<8>, 0>(h, a, split, r); break;
-  }
+  if (h->static_kind == 1) return early ? launch_rollout_t<Ref4Table, kPrefetch>(h, a, lanes, r) : launch_rollout_t<Ref4Table, 0>(h, a, lanes, r);
+  if (h->static_kind == 2) return early ? launch_rollout_t<Dh7Table, kPrefetch>(h, a, lanes, r) : launch_rollout_t<Dh7Table, 0>(h, a, lanes, r);
+  MT_DISPATCH_D(h->D, launch_rollout_d, h, a, lanes, r);
 }
 
 // The rollout kernels implement the default trigonometry and the reference's frame rows only.
@@ -1037,30 +1035,41 @@ int mt_destroy(mt_handle h) {
   return MT_OK;
 }
 
+// What mt_step_kernel_name and mt_describe_dispatch report: the plans of a sampled-action launch of the whole batch and of
+// one chain's span (the same values launch_step resolves; "trig" is the handle's, which the LDS-table and runtime-frame
+// kernels do not all implement: plan_step).
+static StepPlan batch_plan(const mt_engine* h) { return plan_step(h, mt_engine::kBatch, h->n, true, false); }
+static StepPlan chain_plan(const mt_engine* h) { return plan_step(h, mt_engine::kChain, chain_span(h, h->chains), true, false); }
+static std::string table_name(const mt_engine* h) {
+  const char* tbl = h->static_kind == 1 ? "Ref4Table" : (h->static_kind == 2 ? "Dh7Table" : nullptr);
+  return tbl ? tbl : (h->custom_frames ? "RtTableF<" : "RtTable<") + std::to_string(h->D) + ">";
+}
+// mt_rollout's multi-step launches run per chain only where MT_CHAINS asks for it
+static int multi_step_lanes(const mt_engine* h) {
+  return h->sched[(h->chains > 1 && h->chains_forced) ? mt_engine::kChain : mt_engine::kBatch].rollout_lanes;
+}
+
 const char* mt_step_kernel_name(mt_handle h) {
   if (!h) return "";
-  const char* tbl = h->static_kind == 1 ? "Ref4Table" : (h->static_kind == 2 ? "Dh7Table" : nullptr);
-  std::string table = tbl ? tbl : (h->custom_frames ? "RtTableF<" : "RtTable<") + std::to_string(h->D) + ">";
-  if (h->trig == 0 && !h->lds_table && h->split)
-    h->kernel_name = "step_split_kernel<" + table + ", L=" + std::to_string(h->split) + (h->trig_steps ? ", tt=1>" : ">");
+  const std::string table = table_name(h);
+  const StepVariant v = batch_plan(h).v;
+  if (v.lanes > 1)
+    h->kernel_name = "step_split_kernel<" + table + ", L=" + std::to_string(v.lanes) + (v.tt ? ", tt=1>" : ">");
   else
-    h->kernel_name = "step_kernel<" + table + ", trig=" + std::to_string(h->trig) + ", lds=" + (h->lds_table ? "true" : "false") +
-                     ", pf=" + ((h->trig == 0 && !h->lds_table && h->prefetch) ? std::to_string(kPrefetch) : std::string("0")) +
-                     ((h->trig == 0 && !h->lds_table && h->trig_steps) ? ", tt=1" : "") +
-                     ((h->trig == 0 && !h->lds_table && h->prefetch && h->cfg.n_envs >= h->flat_from) ? ", flat=1>" : ">");
+    h->kernel_name = "step_kernel<" + table + ", trig=" + std::to_string(h->trig) + ", lds=" + (v.lds ? "true" : "false") +
+                     ", pf=" + std::to_string(v.pf) + (v.tt ? ", tt=1" : "") + (v.flat ? ", flat=1>" : ">");
   const bool multi_one_chain = h->multi_k > 1 && fusable(h) && !h->chains_forced;  // mt_rollout does not use the chains then
-  if (h->chains > 1 && !multi_one_chain)  // what mt_rollout launches instead: the schedule for a chain's env count, on row views
+  if (h->chains > 1 && !multi_one_chain) {  // what mt_rollout launches instead: the schedule for a chain's env count, on row views
+    const StepPlan c = chain_plan(h);
     h->kernel_name += " [mt_rollout: " + std::to_string(h->chains) + " chains of " + std::to_string(chain_span(h, h->chains)) +
-                      " envs, " + (h->trig == 0 && !h->lds_table && h->chain_split ? "L=" + std::to_string(h->chain_split)
-                                   : std::string(h->trig == 0 && !h->lds_table && h->chain_prefetch
-                                                     ? (chain_span(h, h->chains) >= h->flat_from ? "pf=8, flat=1" : "pf=8") : "pf=0")) +
-                      ((h->trig == 0 && !h->lds_table && !h->chain_split && h->chain_prefetch && h->trig_steps &&
-                        step_blocks_per_cu(h, chain_span(h, h->chains)) > 0)
-                           ? ", " + std::to_string(step_blocks_per_cu(h, chain_span(h, h->chains))) + " blocks/CU" : std::string()) + "]";
+                      " envs, " + (c.v.lanes > 1 ? "L=" + std::to_string(c.v.lanes)
+                                                 : "pf=" + std::to_string(c.v.pf) + (c.v.flat ? ", flat=1" : "")) +
+                      (c.blocks_per_cu > 0 ? ", " + std::to_string(c.blocks_per_cu) + " blocks/CU" : std::string()) + "]";
+  }
   if (h->multi_k > 1 && fusable(h)) {  // what mt_rollout launches on small shards instead of one step kernel per step
-    const int sp = (h->chains > 1 && h->chains_forced) ? h->chain_rollout_split : h->rollout_split;
+    const int sp = multi_step_lanes(h);
     h->kernel_name += " [mt_rollout: " + std::to_string(h->multi_k) + " steps per launch, " +
-                      (sp ? "rollout_split_kernel L=" + std::to_string(sp) : std::string("rollout_kernel")) + "]";
+                      (sp > 1 ? "rollout_split_kernel L=" + std::to_string(sp) : std::string("rollout_kernel")) + "]";
   }
   return h->kernel_name.c_str();
 }
@@ -1071,9 +1080,8 @@ const char* mt_describe_dispatch(mt_handle h) {
   auto num = [](long long v) { return std::to_string(v); };
   auto b = [](bool v) { return std::string(v ? "true" : "false"); };
   const int64_t span = chain_span(h, h->chains);
-  const char* tbl = h->static_kind == 1 ? "Ref4Table" : (h->static_kind == 2 ? "Dh7Table" : nullptr);
-  const std::string table = tbl ? tbl : (h->custom_frames ? "RtTableF<" : "RtTable<") + std::to_string(h->D) + ">";
-  const bool rec = h->trig == 0 && !h->lds_table;   // the default recurrence kernels: the only ones with schedules
+  const std::string table = table_name(h);
+  const StepPlan sb = batch_plan(h), sc = chain_plan(h);
   const bool multi = h->multi_k > 1 && fusable(h);
   const bool graph = h->graph_mode > 0 || (h->graph_mode < 0 && h->n <= h->graph_max);
   std::string caps = "[";
@@ -1083,19 +1091,18 @@ const char* mt_describe_dispatch(mt_handle h) {
   d = "{\"n_envs\":" + num(h->n) + ",\"ld\":" + num(h->ld) + ",\"dof\":" + num(h->D) + ",\"targets\":" + num(h->K) +
       ",\"table\":\"" + table + "\",\"trig\":" + num(h->trig) + ",\"lds_table\":" + b(h->lds_table) + ",\"custom_frames\":" + b(h->custom_frames) +
       // one launch per step: mt_step / mt_step_random on a one-chain handle
-      ",\"step\":{\"lanes_per_env\":" + num(rec && h->split ? h->split : 1) + ",\"prefetch\":" + b(rec && !h->split && h->prefetch) +
-      ",\"trig_table\":" + b(rec && h->trig_steps) + ",\"flat\":" + b(rec && !h->split && h->prefetch && h->n >= h->flat_from) + "}" +
+      ",\"step\":{\"lanes_per_env\":" + num(sb.v.lanes) + ",\"prefetch\":" + b(sb.v.pf != 0) +
+      ",\"trig_table\":" + b(sb.v.tt) + ",\"flat\":" + b(sb.v.flat) + "}" +
       // per-chain calls: mt_rollout, mt_step, mt_sample_actions, mt_set_actions(device), mt_reset_random
       ",\"chains\":{\"count\":" + num(h->chains) + ",\"span\":" + num(h->chains > 1 ? span : h->n) + ",\"lazy\":" + b(h->lazy_chains) +
-      ",\"lanes_per_env\":" + num(rec && h->chain_split ? h->chain_split : 1) + ",\"prefetch\":" + b(rec && !h->chain_split && h->chain_prefetch) +
-      ",\"flat\":" + b(rec && !h->chain_split && h->chain_prefetch && span >= h->flat_from) +
-      ",\"blocks_per_cu\":" + num(h->chains > 1 && rec && !h->chain_split && h->chain_prefetch && h->trig_steps ? step_blocks_per_cu(h, span) : 0) + "}" +
+      ",\"lanes_per_env\":" + num(sc.v.lanes) + ",\"prefetch\":" + b(sc.v.pf != 0) + ",\"flat\":" + b(sc.v.flat) +
+      ",\"blocks_per_cu\":" + num(h->chains > 1 ? sc.blocks_per_cu : 0) + "}" +
       ",\"rollout\":{\"form\":\"" + (multi ? "multi_step" : (h->chains > 1 ? "chained_steps" : (graph ? "graph_replay" : "launch_per_step"))) +
       "\",\"steps_per_launch\":" + num(multi ? h->multi_k : 1) + ",\"graph\":" + b(!multi && graph) +
-      ",\"lanes_per_env\":" + num(std::max(1, multi ? ((h->chains > 1 && h->chains_forced) ? h->chain_rollout_split : h->rollout_split) : (rec ? (h->chains > 1 ? h->chain_split : h->split) : 0))) +
+      ",\"lanes_per_env\":" + num(multi ? multi_step_lanes(h) : (h->chains > 1 ? sc : sb).v.lanes) +
       ",\"chains\":" + num(multi && !h->chains_forced ? 1 : h->chains) +
       ",\"absorbs_reset\":" + b(h->defer_reset && (multi || chained_rollout_absorbs_reset(h))) + ",\"writes_snapshot\":" + b(h->snap_in_rollout && (multi || (h->chains > 1 && !graph && !h->trace))) + "}" +
-      ",\"fused\":{\"usable\":" + b(fusable(h)) + ",\"lanes_per_env\":" + num(h->rollout_split ? h->rollout_split : 1) + "}" +
+      ",\"fused\":{\"usable\":" + b(fusable(h)) + ",\"lanes_per_env\":" + num(h->sched[mt_engine::kBatch].rollout_lanes) + "}" +
       ",\"reset\":{\"lanes_per_env\":" + num(h->reset_split ? 4 : 1) + "}" +
       ",\"overrides\":\"" + h->overrides + "\"" +
       ",\"policy\":{\"step_split4_max\":" + num(P.step_split4_max) + ",\"step_split2_max\":" + num(P.step_split2_max) +
@@ -1493,7 +1500,7 @@ int mt_env_step(mt_handle h, int64_t env, const float* action, float* obs, int32
   const size_t pitch = (size_t)h->ld * 4;
   // column `env` of the D action rows <- D host floats
   MT_HIP(h, hipMemcpy2DAsync(a.actions, pitch, action, 4, 4, (size_t)h->D, hipMemcpyHostToDevice, h->stream));
-  launch_step(h, a, h->trace ? h->trace + env : nullptr, false, false);
+  launch_step(h, mt_engine::kOneEnv, a, h->trace ? h->trace + env : nullptr, false);
   h->args.flags &= ~kFlagWholeGoals;
   int rc = check_launch(h, "step_kernel (one env)");
   if (rc) return rc;
@@ -1598,7 +1605,7 @@ static int rollout_graph(mt_handle h, int T, uint64_t seed, int chains, const mt
       for (int s = 0; s < T; ++s) {
         StepArgs as = a;
         as.major = (uint32_t)s;
-        launch_step(h, as, nullptr, true, true);
+        launch_step(h, mt_engine::kBatch, as, nullptr, true);
       }
     }
     h->stream = launch_stream;
@@ -1703,7 +1710,7 @@ int mt_rollout(mt_handle h, int n_steps, uint64_t seed, uint32_t step_idx0) {
           RolloutArgs r = args_of(s0);
           if (r.snap) r.snap += off;
           if (fresh && s0 == 0 && c > 0 && rc == MT_OK) rc = order_behind_inplace_gather(h, h->stream);
-          if (rc == MT_OK) launch_rollout(h, args_for_range(h, a, off, std::min(span, h->n - off)), h->chain_rollout_split, r, h->rollout_early);
+          if (rc == MT_OK) launch_rollout(h, args_for_range(h, a, off, std::min(span, h->n - off)), h->sched[mt_engine::kChain].rollout_lanes, r, h->rollout_early);
         }
       }
       h->stream = root;
@@ -1713,7 +1720,7 @@ int mt_rollout(mt_handle h, int n_steps, uint64_t seed, uint32_t step_idx0) {
     } else {
       rc = join_chains(h);
       if (rc) return rc;
-      for (int s0 = 0; s0 < n_steps; s0 += h->multi_k) launch_rollout(h, a, h->rollout_split, args_of(s0), h->rollout_early);
+      for (int s0 = 0; s0 < n_steps; s0 += h->multi_k) launch_rollout(h, a, h->sched[mt_engine::kBatch].rollout_lanes, args_of(s0), h->rollout_early);
       rc = check_launch(h, "rollout_kernel (mt_rollout)");
     }
     if (rc) return rc;
@@ -1855,7 +1862,7 @@ int mt_rollout_fused(mt_handle h, int n_steps, uint64_t seed, uint32_t step_idx0
     if (rcg) return rcg;
   }
   RolloutArgs r{n_steps, step_idx0, auto_reset ? 1u : 0u, h->cfg.radius, 0u, 0u, 0u, 0u, nullptr};
-  launch_rollout(h, h->args, h->rollout_split, r);
+  launch_rollout(h, h->args, h->sched[mt_engine::kBatch].rollout_lanes, r);
   return check_launch(h, "rollout_kernel");
 }
 

@@ -47,13 +47,18 @@ struct mt_engine {
   int trig = 0;          // 0 recurrence, 1 polynomial sincos per sub-step, 2 hardware trig per sub-step
   bool lds_table = false;
   bool custom_frames = false;  // obs_frame / ee_frame are not the reference's last two rows: RtTableF kernels
-  int split = 0;          // step_split_kernel<..., L>: one env over L = 2 or 4 lanes (0 = one env per lane)
-  int rollout_split = 0;  // the same choice for rollout_split_kernel (it pays up to larger batches: mt_create)
+  // The kernel schedule of one scope of launches, picked for that scope's env count: the whole batch, or one chain of a
+  // multi-chain call (a chain is a batch of chain_span() envs).  Written by choose_dispatch only; launches read it.
+  struct Schedule {
+    int step_lanes = 1;     // step_split_kernel<..., L>: one env over L = 2 or 4 lanes (1 = one env per lane)
+    bool prefetch = false;  // step_kernel<..., PF = kPrefetch>: target loads requested ahead of the kinematics
+    int rollout_lanes = 1;  // the same choice as step_lanes for rollout_split_kernel (it pays up to larger batches)
+  };
+  enum Scope { kBatch = 0, kChain = 1, kOneEnv = 2 };  // kOneEnv: the single-env view, on the batch's schedule
+  Schedule sched[2];  // [kBatch], [kChain] (equal on a one-chain handle)
   int blocks_per_cu_override = -1;  // MT_BLOCKS_PER_CU: occupancy cap of the PF + TT step launches (engine.hip: step_blocks_per_cu)
   int64_t flat_from = 393216;  // launches of the prefetch kernel over at least this many envs take its FLAT form (kernels.h,
                                // LaneOffset<false>: the HBM-bound regime); MT_FLAT_FROM overrides
-  bool prefetch_forced = false;
-  bool prefetch = false;  // step_kernel<..., PF = kPrefetch>: target loads requested ahead of the kinematics
   bool goals_exposed = false;  // mt_device_ptr(MT_F_GOALS) was handed out: joint angles may change without the library knowing
   // The target codes (StepArgs::codes) match MT_F_POINTS for every env: set by a full random reset (it writes both), kept by
   // the re-arm of finished envs and by the step launches that read codes (step_kernel<.., CODES>), cleared by everything else
@@ -102,9 +107,6 @@ struct mt_engine {
   // mt_sync join them; mt_device_ptr does not.
   int chains = 1;
   bool chains_forced = false;   // MT_CHAINS was given (the multi-step mt_rollout then runs per chain as well)
-  int chain_split = 0;          // the step-kernel schedule of a chain's launches is picked for the CHAIN's env count
-  bool chain_prefetch = false;
-  int chain_rollout_split = 0;  // ... and the rollout-kernel schedule of a chain's multi-step launches
   int multi_k = 1;              // mt_rollout: steps per launch on small shards (rollout kernels), 1 = one launch per step
   bool rollout_early = true;    // ... with the rollout kernels' RPF prologue (first step under the state loads; static tables)
   // The episode boundary folded into mt_rollout's multi-step launches (kernels.h RolloutArgs):
