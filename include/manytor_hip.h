@@ -212,6 +212,8 @@ MT_API int mt_env_step(mt_handle h, int64_t env, const float* action, float* obs
 /* Number of (env, step) pairs so far whose staged action was not a finite angle of magnitude <= 32768 degrees (NaN,
  * +-inf from a diverging policy ...).  Such an env holds its pose for that step instead of poisoning its state.
  * Synchronises.  The reference has no such check (numpy would propagate the NaN into goals, manytor.py:184).
+ * Every angle inside that range is a full citizen: positions and the ground test keep their 1e-4 accuracy against the
+ * fp64 reference up to +-32768 degrees (beyond +-180 the kernels form the route's angles in double, modulo 360).
  * Also counts the targets mt_reset dropped because a coordinate handed over in device memory was NaN / infinite. */
 MT_API int mt_bad_action_count(mt_handle h, uint64_t* count);
 /* The same with the action drawn in-kernel (results bit-identical to mt_sample_actions followed by
@@ -256,7 +258,8 @@ MT_API int mt_get(mt_handle h, int field, void* dst, int64_t dst_bytes, int is_d
  * arrays (attribute assignment on the reference objects, e.g. manytor.py:243), and -- for restoring a checkpoint --
  * DONE (u8 N; the ballot words are rebuilt), EPISODES (u32 N), LAST_RETURN (f32 N), RETURN_RING (f32 N,R).
  * Floating-point input is screened: NaN / +-inf anywhere, or a joint angle beyond +-32768 degrees, is
- * MT_ERR_INVALID_ARG and nothing is written (the kernels assume finite state). */
+ * MT_ERR_INVALID_ARG and nothing is written (the kernels assume finite state).  A pose anywhere inside +-32768
+ * degrees is stepped from with the accuracy of one inside +-180. */
 MT_API int mt_set(mt_handle h, int field, const void* src, int64_t src_bytes);
 /* The episode index every env was given by the last full reset (finished-episode counts and return-ring slots are
  * relative to it): mt_reset / mt_reset_random set it; a checkpoint restore sets it back with this call. */

@@ -605,11 +605,11 @@ __device__ __forceinline__ void prev_pose_sincos(const Tbl& t, const float (&g)[
   for (int j = 1; j < JN; ++j) sincos_deg(g[j] + t.off(j), sF[j], cF[j]);
 }
 
-template <class Tbl, int TRIG, bool CACHED = false, bool TABLE = false>
-__device__ __forceinline__ float route_kinematics(const Tbl& t, int S, float inv_sm1, const float (&g)[Tbl::D],
-                                                  const float (&act)[Tbl::D], float (&el)[3], float (&e)[3],
-                                                  PoseCache<Tbl::D>* cache = nullptr, bool cache_valid = false,
-                                                  const SinCos* trig = nullptr, bool prev_whole = false) {
+template <class Tbl, int TRIG, bool CACHED, bool TABLE>
+__device__ __forceinline__ float route_kinematics_narrow(const Tbl& t, int S, float inv_sm1, const float (&g)[Tbl::D],
+                                                         const float (&act)[Tbl::D], float (&el)[3], float (&e)[3],
+                                                         PoseCache<Tbl::D>* cache, bool cache_valid, const SinCos* trig,
+                                                         bool prev_whole) {
   constexpr int D = Tbl::D;
   constexpr int JN = ZJoints<Tbl>::value;
   constexpr bool kSequential = (TRIG == 0 || TRIG == 5) && D >= 6;
@@ -761,6 +761,100 @@ __device__ __forceinline__ float route_kinematics(const Tbl& t, int S, float inv
     }
   }
   return zmin;
+}
+
+// ---------------------------------------------------------------------------
+// Routes with an end beyond +-180 degrees (mt_math.h: wide_angle).  Staged actions, and the poses they leave behind,
+// are accepted up to +-32 768 degrees, where the fp32 increment (act - g) / (S - 1), the sums g + k * increment and
+// g + offset all round by more than the position tolerance.  Such a route is evaluated pose by pose from angles formed
+// in double and reduced modulo 360 there (sincos_deg_route): S sincos per joint instead of the recurrence, no drift,
+// the per-pose accuracy of a route inside +-180.  An end within +-180 keeps its fp32 sum (sincos_deg_off), so the final
+// pose -- elbow, end effector, observations, the PoseCache handed to the next step -- has the bits of the narrow form
+// whenever the ACTION is narrow, wherever the route started.
+//
+// Cold by construction: `any joint of g or act wide` is tested per lane and the branch is taken per WAVE (__any), so a
+// wave without such a lane executes the narrow form alone, unchanged, and the two forms never share registers: a
+// batch within +-180 gets the bits and the kernel the resources it had.  A wave WITH such a lane takes this form as a
+// whole.  Its narrow lanes lose nothing (their ends are the narrow form's bits, their interior poses have no recurrence
+// drift), but their z-minimum is then this form's, not the recurrence's: within the same 1e-4 of the reference, so
+// the ground flag can differ from a narrow wave's only inside the guard band.
+// ---------------------------------------------------------------------------
+// The test itself is on the hot path of every step, so it is kept to what can be wide at all: not the pose while the
+// host knows the whole batch to sit on whole degrees in [-180, 180) (kFlagWholeGoals, a launch constant: the steps of a
+// sampled rollout test one scalar flag), not an action out of the whole-degree table (TABLE: drawn in-kernel, always in
+// [-180, 180)).  The rest is one running maximum of magnitudes (v_max3_f32 with |.| modifiers) and one compare.
+template <class Tbl, bool TABLE>
+__device__ __forceinline__ bool wide_route(const float (&g)[Tbl::D], const float (&act)[Tbl::D], bool prev_whole) {
+  float reach = 0.f;
+  if (!prev_whole) {
+#pragma unroll
+    for (int j = 0; j < Tbl::D; ++j) reach = fmaxf(reach, __builtin_fabsf(g[j]));
+  }
+  if (!TABLE) {
+#pragma unroll
+    for (int j = 0; j < Tbl::D; ++j) reach = fmaxf(reach, __builtin_fabsf(act[j]));
+  }
+  return wide_angle(reach);
+}
+
+template <class Tbl, bool CACHED>
+__device__ __forceinline__ float route_kinematics_wide(const Tbl& t, int S, const float (&g)[Tbl::D],
+                                                       const float (&act)[Tbl::D], float (&el)[3], float (&e)[3],
+                                                       PoseCache<Tbl::D>* cache) {
+  constexpr int D = Tbl::D;
+  constexpr int JN = ZJoints<Tbl>::value;
+  float s[D], c[D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) {  // chain_z reads joints 1 .. JN-1 only
+    s[j] = 0.f;
+    c[j] = 1.f;
+  }
+  // k = 0 (the previous pose, evaluated again: manytor.py:182-192) .. S-2.  The action's pose comes last, as in the
+  // sequential schedule of the narrow form: what it leaves behind (el, e, the cache) is not held across the loop.
+  float zmin = 0.f;
+  const double inv = 1.0 / (double)(S - 1);
+  for (int k = 0; k < S - 1; ++k) {
+    const double frac = (double)k * inv;
+#pragma unroll
+    for (int j = 1; j < JN; ++j) {
+      // (opaque copies: the conversions to double are redone per pose instead of being kept, two doubles per joint, across
+      // the loop -- this form has to fit the register budget the narrow form sets for the kernel)
+      float gj = g[j], aj = act[j];
+      asm volatile("" : "+v"(gj), "+v"(aj));
+      sincos_deg_route(gj, aj, frac, t.off(j), s[j], c[j]);
+    }
+    float zo, ze;
+    chain_z<Tbl>(s, c, t, zo, ze);
+    zmin = (k == 0) ? fminf(zo, ze) : fminf(zmin, fminf(zo, ze));
+  }
+  // k = S-1: the action itself, full chain
+  float p[D][3];
+#pragma unroll
+  for (int j = 0; j < D; ++j) sincos_deg_off(act[j], t.off(j), s[j], c[j]);
+  chain_all<Tbl>(s, c, t, p);
+  pick_frames<Tbl>(t, p, el, e);
+  if (CACHED) {
+#pragma unroll
+    for (int j = 1; j < JN; ++j) {
+      cache->s[j] = s[j];
+      cache->c[j] = c[j];
+    }
+    cache->zmin = fminf(el[2], e[2]);
+  }
+  zmin = fminf(zmin, fminf(el[2], e[2]));
+  return zmin;
+}
+
+template <class Tbl, int TRIG, bool CACHED = false, bool TABLE = false>
+__device__ __forceinline__ float route_kinematics(const Tbl& t, int S, float inv_sm1, const float (&g)[Tbl::D],
+                                                  const float (&act)[Tbl::D], float (&el)[3], float (&e)[3],
+                                                  PoseCache<Tbl::D>* cache = nullptr, bool cache_valid = false,
+                                                  const SinCos* trig = nullptr, bool prev_whole = false) {
+  if constexpr (TRIG <= 2) {  // (3, 4, 5: diagnostic builds, timing only)
+    if (__builtin_expect(__any(wide_route<Tbl, TABLE>(g, act, prev_whole)), 0))
+      return route_kinematics_wide<Tbl, CACHED>(t, S, g, act, el, e, cache);
+  }
+  return route_kinematics_narrow<Tbl, TRIG, CACHED, TABLE>(t, S, inv_sm1, g, act, el, e, cache, cache_valid, trig, prev_whole);
 }
 
 // An env finished its episode `episode` with return `ret` and is being re-armed: keep the return in the ring
@@ -1028,12 +1122,11 @@ __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) voi
 // the env's sub-lanes at the end (lane = q * (64 / L) + e, so the partners sit 64 / L, 2 * 64 / L ... lanes apart).
 // Every sub-lane computes the endpoint sincos and the full chain at the final pose itself (it needs elbow and end
 // effector for its targets).  -(s * -sd) == s * sd exactly and min is order-free => the bits of route_kinematics.
-template <class Tbl, int L, bool CACHED, bool TABLE = false>
-__device__ __forceinline__ float route_kinematics_split(const Tbl& t, int S, float inv_sm1, const float (&g)[Tbl::D],
-                                                        const float (&act)[Tbl::D], bool backward, float (&el)[3],
-                                                        float (&e)[3], PoseCache<Tbl::D>* cache = nullptr,
-                                                        bool cache_valid = false, const SinCos* trig = nullptr,
-                                                        bool prev_whole = false) {
+template <class Tbl, int L, bool CACHED, bool TABLE>
+__device__ __forceinline__ float route_kinematics_split_narrow(const Tbl& t, int S, float inv_sm1, const float (&g)[Tbl::D],
+                                                               const float (&act)[Tbl::D], bool backward, float (&el)[3],
+                                                               float (&e)[3], PoseCache<Tbl::D>* cache, bool cache_valid,
+                                                               const SinCos* trig, bool prev_whole) {
   constexpr int D = Tbl::D;
   constexpr int JN = ZJoints<Tbl>::value;
   constexpr int EPW = 64 / L;
@@ -1097,6 +1190,20 @@ __device__ __forceinline__ float route_kinematics_split(const Tbl& t, int S, flo
 #pragma unroll
   for (int sh = EPW; sh < 64; sh <<= 1) zmin = fminf(zmin, __shfl_xor(zmin, sh));
   return zmin;
+}
+
+// A wave with a wide route (see route_kinematics_wide): every sub-lane of an env walks all S poses itself -- the sub-lanes
+// hold the same pose and action, so they agree on the result, and there is nothing to combine.
+template <class Tbl, int L, bool CACHED, bool TABLE = false>
+__device__ __forceinline__ float route_kinematics_split(const Tbl& t, int S, float inv_sm1, const float (&g)[Tbl::D],
+                                                        const float (&act)[Tbl::D], bool backward, float (&el)[3],
+                                                        float (&e)[3], PoseCache<Tbl::D>* cache = nullptr,
+                                                        bool cache_valid = false, const SinCos* trig = nullptr,
+                                                        bool prev_whole = false) {
+  if (__builtin_expect(__any(wide_route<Tbl, TABLE>(g, act, prev_whole)), 0))
+    return route_kinematics_wide<Tbl, CACHED>(t, S, g, act, el, e, cache);
+  return route_kinematics_split_narrow<Tbl, L, CACHED, TABLE>(t, S, inv_sm1, g, act, backward, el, e, cache, cache_valid, trig,
+                                                              prev_whole);
 }
 
 // ---------------------------------------------------------------------------
@@ -1280,8 +1387,16 @@ __global__ __launch_bounds__(kBlock) void trace_kernel(const StepArgs a, float* 
   for (int j = 0; j < D; ++j) st[j] = (act[j] - g[j]) * a.inv_sm1;
   for (int k = 0; k < a.S; ++k) {
     float s[D], c[D], p[D][3];
+    const double frac = (double)k / (double)(a.S - 1);
 #pragma unroll
     for (int j = 0; j < D; ++j) {
+      if (wide_angle(g[j]) | wide_angle(act[j])) {  // see route_kinematics_wide
+        if (k == a.S - 1)
+          sincos_deg_off(act[j], t.off(j), s[j], c[j]);
+        else
+          sincos_deg_route(g[j], act[j], frac, t.off(j), s[j], c[j]);
+        continue;
+      }
       const float pose = (k == a.S - 1) ? act[j] : __builtin_fmaf((float)k, st[j], g[j]);  // np.linspace, manytor.py:182
       sincos_deg(pose + t.off(j), s[j], c[j]);
     }
@@ -2037,7 +2152,7 @@ __global__ __launch_bounds__(kBlock) void observe_kernel(const StepArgs a) {
   const int64_t ld = a.ld;
   float s[D], c[D], p[D][3];
 #pragma unroll
-  for (int j = 0; j < D; ++j) sincos_deg((a.goals + j * ld)[i] + a.dh.off_deg[j], s[j], c[j]);
+  for (int j = 0; j < D; ++j) sincos_deg_off((a.goals + j * ld)[i], a.dh.off_deg[j], s[j], c[j]);
   const RtTableF<D> t{a.dh};
   chain_all<RtTableF<D>>(s, c, t, p);
   float el[3], e_unused[3];
@@ -2071,7 +2186,7 @@ __global__ __launch_bounds__(kBlock) void check_done_kernel(const StepArgs a) {
   const int64_t ld = a.ld;
   float s[D], c[D], p[D][3];
 #pragma unroll
-  for (int j = 0; j < D; ++j) sincos_deg((a.goals + j * ld)[i] + a.dh.off_deg[j], s[j], c[j]);
+  for (int j = 0; j < D; ++j) sincos_deg_off((a.goals + j * ld)[i], a.dh.off_deg[j], s[j], c[j]);
   const RtTableF<D> t{a.dh};
   chain_all<RtTableF<D>>(s, c, t, p);
   float el_unused[3], e[3];
@@ -2098,7 +2213,7 @@ __global__ __launch_bounds__(kBlock) void joints_kernel(const StepArgs a, float*
   const int64_t ld = a.ld;
   float s[D], c[D], p[D][3];
 #pragma unroll
-  for (int j = 0; j < D; ++j) sincos_deg((a.goals + j * ld)[i] + a.dh.off_deg[j], s[j], c[j]);
+  for (int j = 0; j < D; ++j) sincos_deg_off((a.goals + j * ld)[i], a.dh.off_deg[j], s[j], c[j]);
   chain_all<RtTable<D>>(s, c, RtTable<D>{a.dh}, p);
   float* o = out + (int64_t)i * (3 * D);
 #pragma unroll
@@ -2166,7 +2281,7 @@ __global__ __launch_bounds__(kBlock) void fk_kernel(const FkArgs a) {
     float ang = a.angles[(int64_t)i * a.dof + j];
     if (a.radians) ang *= 57.29577951308232f;
     float s, c;
-    sincos_deg(ang + a.dh.off_deg[j], s, c);
+    sincos_deg_off(ang, a.dh.off_deg[j], s, c);
     for (int q = 0; q < 3; ++q) {
       const float nx = __builtin_fmaf(X[q], c, Y[q] * s);
       const float tt = __builtin_fmaf(Y[q], c, -(X[q] * s));
@@ -2212,9 +2327,16 @@ __global__ __launch_bounds__(kBlock) void route_trace_kernel(const TraceArgs a) 
   for (int j = 0; j < a.dof; ++j) {
     const float g = a.prev[env * a.dof + j], act = a.action[env * a.dof + j];
     // np.linspace: start + k * step, last element = stop exactly (manytor.py:182)
-    const float pose = (k == a.S - 1) ? act : __builtin_fmaf((float)k, (act - g) * inv, g);
     float s, c;
-    sincos_deg(pose + a.dh.off_deg[j], s, c);
+    if (wide_angle(g) | wide_angle(act)) {  // see route_kinematics_wide
+      if (k == a.S - 1)
+        sincos_deg_off(act, a.dh.off_deg[j], s, c);
+      else
+        sincos_deg_route(g, act, (double)k / (double)(a.S - 1), a.dh.off_deg[j], s, c);
+    } else {
+      const float pose = (k == a.S - 1) ? act : __builtin_fmaf((float)k, (act - g) * inv, g);
+      sincos_deg(pose + a.dh.off_deg[j], s, c);
+    }
     for (int q = 0; q < 3; ++q) {
       const float nx = __builtin_fmaf(X[q], c, Y[q] * s);
       const float tt = __builtin_fmaf(Y[q], c, -(X[q] * s));

@@ -85,6 +85,33 @@ __device__ __forceinline__ void sincos_deg(float x, float& s, float& c) {
   c = __uint_as_float(__float_as_uint(cc) ^ flip);
 }
 
+// ---- angles beyond +-180 degrees (staged actions and poses are accepted up to +-32 768) ------------------------------
+// sincos_deg is exact in its reduction for any float it is GIVEN; what goes wrong far out is every fp32 sum formed
+// before it.  The ulp of an angle near 32 768 is 0.002-0.004 degrees (7e-5 rad: 2e-3 at the tip of a 27-long link), so
+// pose + joint offset, (action - pose) / (S - 1) and pose + k * increment each round by more than the whole position
+// tolerance (1e-4).  A pose matters only modulo 360, fp64 holds all of these sums to 1e-11
+// degrees, and the remainder x - 360 rint(x / 360) is exact in fp64: so a WIDE angle takes the sum in double, drops the
+// whole turns there and rounds once, to a float within +-180 -- the precision every angle inside +-180 has anyway.
+// Angles within +-180 never come here: they keep the fp32 expressions, and with them their bits.
+__device__ __forceinline__ bool wide_angle(float x) { return __builtin_fabsf(x) > 180.0f; }
+__device__ __forceinline__ float drop_turns(double x) {
+  const double q = __builtin_rint(x * (1.0 / 360.0));
+  return (float)__builtin_fma(q, -360.0, x);  // exact before the conversion: |result| <= 180 (+ an ulp of x / 360)
+}
+// sin and cos of (x + off) degrees: a pose angle plus its joint's theta offset
+__device__ __forceinline__ void sincos_deg_off(float x, float off, float& s, float& c) {
+  if (wide_angle(x))
+    sincos_deg(drop_turns((double)x + (double)off), s, c);
+  else
+    sincos_deg(x + off, s, c);
+}
+// sin and cos of pose k of S on the straight line g -> act (np.linspace: g + k * (act - g) / (S - 1)), plus off, for a
+// route with a wide end.  frac = k / (S - 1) in double.
+__device__ __forceinline__ void sincos_deg_route(float g, float act, double frac, float off, float& s, float& c) {
+  const double pose = __builtin_fma(frac, (double)act - (double)g, (double)g + (double)off);
+  sincos_deg(drop_turns(pose), s, c);
+}
+
 // Hardware transcendental path: v_sin_f32 / v_cos_f32 take REVOLUTIONS.
 // Quarter-rate, ~1e-6 absolute; only used where a 1e-3 guard band applies
 // (the ground flag of intermediate sub-steps) and only under MT_FLAG_HW_TRIG.
