@@ -297,7 +297,10 @@ MT_API int mt_gather_returns(mt_handle h, int field, int row, float* dst, int64_
  * mt_gather_returns_begin lets the calling thread run at most ONE exchange ahead of the device: if the exchange before the one
  * just begun has not finished yet it waits for it (the device still holds a whole episode of queued work then), so that the
  * next episode needs neither a snapshot launch nor a stream wait between its steps and the gather.  MT_GATHER_THROTTLE=0
- * never waits (the snapshot is then a launch of its own whenever the host is further ahead). */
+ * never waits (the snapshot is then a launch of its own whenever the host is further ahead).
+ * On a caller's stream (mt_set_stream), and while that stream is being captured, mt_rollout does not write the snapshot and
+ * this call always copies the row in stream order: a write queued on that stream between the two calls (a torch op on a
+ * mt_device_ptr view, say) is part of what is gathered. */
 MT_API int mt_gather_returns_begin(mt_handle h, int field, int row, float* dst, int64_t dst_elems);
 MT_API int mt_gather_returns_wait(mt_handle h, int host_wait, float* elapsed_ms);
 /* The same without the snapshot: the exchange on the side stream reads the arena row itself, so nothing is copied on the

@@ -446,8 +446,10 @@ static int gather_begin_impl(mt_handle h, int field, int row, float* dst, int64_
   MT_ON_DEVICE(h, h->cfg.device);
   rc = mt::flush_pending_reset(h);  // (a reset deferred into the next mt_rollout changes the rows this call reads)
   if (rc) return rc;
-  // mt_rollout's last launch already stored the returns to the snapshot row and nothing has touched them since: no copy
-  const bool have_snap = !inplace && h->snap_valid && src == h->args.total_reward && h->snap != nullptr;
+  // mt_rollout's last launch already stored the returns to the snapshot row and nothing has touched them since: no copy.
+  // Trusted on the handle's own stream only (mt::snapshot_trusted): on a caller's stream a write the library never saw may
+  // sit between that launch and this call, and the copy below runs in stream order behind it.
+  const bool have_snap = !inplace && h->snap_valid && mt::snapshot_trusted(h) && src == h->args.total_reward && h->snap != nullptr;
   h->snap_valid = false;
   if (!per_chain) {
     rc = mt::join_chains(h);

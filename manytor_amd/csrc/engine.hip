@@ -216,7 +216,8 @@ static void choose_dispatch(mt_handle h) {
   const int64_t n = cfg->n_envs;
   long long v = 0;
   h->overrides.clear();
-  auto seen = [&](const char* name) { h->overrides += (h->overrides.empty() ? "" : ",") + std::string(name) + "=" + std::getenv(name); };
+  // (the value as it was PARSED, never the raw text: mt_describe_dispatch pastes this into a JSON string)
+  auto seen = [&](const char* name) { h->overrides += (h->overrides.empty() ? "" : ",") + std::string(name) + "=" + std::to_string(v); };
 
   h->trig = (cfg->flags & MT_FLAG_HW_TRIG) ? 2 : ((cfg->flags & MT_FLAG_DIRECT_TRIG) ? 1 : 0);
   if (cfg->flags & MT_FLAG_ABLATE_LOOP) h->trig = (cfg->flags & MT_FLAG_ABLATE_OBS) ? 4 : 3;
@@ -1671,7 +1672,7 @@ int mt_rollout(mt_handle h, int n_steps, uint64_t seed, uint32_t step_idx0) {
     h->reset_pending = false;
     // the snapshot row of the next exchange (double-buffered: engine_internal.h) may be written once the exchange that last
     // read it is known to have finished: asked, never waited for (mt_gather_returns_begin keeps the host informed)
-    bool snap = h->snap_in_rollout && h->snap != nullptr;
+    bool snap = h->snap_in_rollout && h->snap != nullptr && snapshot_trusted(h);  // (own stream only: engine_internal.h)
     const int snap_p = h->snap_next;
     if (snap && !h->snap_free_known[snap_p]) {
       if (hipEventQuery(h->ev_gdone[snap_p]) == hipSuccess) {
@@ -1782,7 +1783,7 @@ int mt_rollout(mt_handle h, int n_steps, uint64_t seed, uint32_t step_idx0) {
     StepArgs a_last = a;
     {
       const int sp = h->snap_next;
-      bool snap = h->snap_in_rollout && h->snap != nullptr && !h->trace;
+      bool snap = h->snap_in_rollout && h->snap != nullptr && !h->trace && snapshot_trusted(h);
       if (snap && !h->snap_free_known[sp]) {
         if (hipEventQuery(h->ev_gdone[sp]) == hipSuccess) {
           h->snap_free_known[sp] = true;

@@ -174,6 +174,22 @@ class DeviceGuard {
 
 inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 
+// May the host know what the gather's snapshot row holds (snap_valid)?  Only while the handle runs on its OWN stream: nobody
+// else can queue work there, so nothing writes MT_F_TOTAL_REWARD between mt_rollout's last launch and the gather without
+// calling the library (the contract on that stream is mt_sync before foreign writes, and mt_sync ends snap_valid).  On a
+// caller's stream the contract is stream order: a torch op on a view taken long ago may sit between the two calls, so
+// mt_rollout does not write the row there and mt_gather_returns_begin copies it in stream order.  Nor under a capture: a
+// call that only captured has stored nothing yet.
+inline bool snapshot_trusted(mt_engine* h) {
+  if (h->stream != h->own_stream) return false;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(h->stream, &st) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return st == hipStreamCaptureStatusNone;
+}
+
 // engine.hip: the handle's stream waits for everything the chain streams still carry (no-op when not forked)
 int join_chains(mt_handle h);
 // engine.hip: a full reset that mt_reset_random deferred into the next mt_rollout is launched now (no-op without one)

@@ -262,7 +262,8 @@ def test_reset_and_snapshot_folded_into_rollout_launches_equal_the_eager_forms(m
     in-place exchange of MT_F_LAST_RETURN, raw device views, fused rollouts, reset_done -- must see exactly what the eager
     reset kernel and the snapshot launch produce: every field, the gathered returns, the ring, bit for bit.  On a caller's
     stream the reset is not deferred (stream order is the contract there; test_step_is_capturable_in_a_hip_graph replays a
-    captured step right behind a reset), the snapshot still rides along."""
+    captured step right behind a reset) and mt_rollout leaves the snapshot to mt_gather_returns_begin, which copies the row in
+    stream order (a torch write between the two calls is gathered: test_gpu_view_writes.py)."""
     table, radius = {"ref": (m.REF_DH_TABLE, 51.3), "dh7": (m.DH7_TABLE, 92.6), "rt5": (RT5, 25.0)}[table_name]
     if chains:
         monkeypatch.setenv("MT_CHAINS", chains)
