@@ -245,6 +245,35 @@ MT_API int mt_rollout(mt_handle h, int n_steps, uint64_t seed, uint32_t step_idx
  * State after the call is bit-identical to the launch-per-step sequence. */
 MT_API int mt_rollout_fused(mt_handle h, int n_steps, uint64_t seed, uint32_t step_idx0, int auto_reset);
 
+/* The same residency for actions the CALLER chose: T steps in one launch, driven by a (T, D, N) block of angles that is
+ * already on the device (a sampling planner's candidates, a recorded episode, an open-loop chunk of a policy).
+ * A committing call behaves as T x (mt_set_actions(tape row t); mt_step), with MT_TAPE_AUTO_RESET as T x (...;
+ * mt_reset_done(seed)): MT_F_* hold the state after T steps and the outputs of the LAST step (MT_F_DONE == 2 for an env
+ * re-armed in it), ring / MT_F_LAST_RETURN / MT_F_EPISODES behave as with mt_rollout_fused(auto_reset), bit for bit.  An
+ * unusable action (NaN, +-inf, beyond +-32768 degrees) makes that env hold its pose for that step and is counted
+ * (mt_bad_action_count).  Intermediate steps neither compute nor store observations; per step the call writes only the
+ * two log bytes, where asked for.  One launch on the handle's stream, no allocation, no host wait: legal under stream
+ * capture.  MT_TAPE_DRY_RUN evaluates only: logs and return_out are written, nothing resident changes (state, MT_F_*
+ * outputs, ring, counters) -- "what would these T actions earn from here?".
+ * MT_ERR_UNSUPPORTED on handles whose flags the rollout kernels do not implement (HW_TRIG, DIRECT_TRIG, DH_IN_LDS,
+ * TRACE, custom frames); MT_ERR_STATE before a reset; n_steps == 0 is a no-op. */
+#define MT_TAPE_AUTO_RESET 0x1u   /* re-arm an env in the step it finishes, as mt_reset_done(seed) after every step would */
+#define MT_TAPE_DRY_RUN    0x2u   /* evaluate only: nothing resident changes (state, MT_F_* outputs, ring, counters) */
+typedef struct mt_tape {
+  int32_t struct_size;      /* = sizeof(mt_tape), checked */
+  int32_t n_steps;          /* T >= 0 */
+  const float* actions;     /* DEVICE, f32, degrees: joint j of env i at step t = actions[(t*D + j)*ld + i] */
+  int64_t ld;               /* row pitch in elements, >= n_envs (no other alignment asked) */
+  int8_t*  reward_log;      /* DEVICE or NULL: reward of env i at step t -> reward_log[t*log_ld + i] */
+  uint8_t* done_log;        /* DEVICE or NULL: 1 where env i finished in step t, else 0 */
+  int64_t log_ld;           /* >= n_envs when a log is given */
+  float* return_out;        /* DEVICE or NULL: (N,) sum of the call's T rewards of env i (across re-arms) */
+  uint64_t seed;            /* keys the targets of re-armed envs (MT_TAPE_AUTO_RESET) */
+  uint32_t flags;           /* MT_TAPE_* */
+  uint32_t reserved;        /* must be 0 */
+} mt_tape;
+MT_API int mt_rollout_tape(mt_handle h, const mt_tape* tape);
+
 /* Environment.get_observations(), manytor.py:141-153, at the current pose (also
  * zeroes the coordinates of dead targets, :148).  Result in MT_F_OBS. */
 MT_API int mt_observe(mt_handle h);

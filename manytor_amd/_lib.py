@@ -77,6 +77,26 @@ class MtConfig(C.Structure):
     ]
 
 
+class MtTape(C.Structure):
+    """mt_tape of include/manytor_hip.h: the argument block of mt_rollout_tape."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_steps", C.c_int32),
+        ("actions", C.c_void_p),
+        ("ld", C.c_int64),
+        ("reward_log", C.c_void_p),
+        ("done_log", C.c_void_p),
+        ("log_ld", C.c_int64),
+        ("return_out", C.c_void_p),
+        ("seed", C.c_uint64),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+TAPE_AUTO_RESET = 0x1
+TAPE_DRY_RUN = 0x2
+
 _HANDLE = C.c_void_p
 
 # name -> (restype, argtypes); exactly the prototypes of include/manytor_hip.h
@@ -105,6 +125,7 @@ PROTOTYPES = {
     "mt_step_random": (C.c_int, [_HANDLE, C.c_uint64, C.c_uint32]),
     "mt_rollout": (C.c_int, [_HANDLE, C.c_int, C.c_uint64, C.c_uint32]),
     "mt_rollout_fused": (C.c_int, [_HANDLE, C.c_int, C.c_uint64, C.c_uint32, C.c_int]),
+    "mt_rollout_tape": (C.c_int, [_HANDLE, C.POINTER(MtTape)]),
     "mt_observe": (C.c_int, [_HANDLE]),
     "mt_check_done": (C.c_int, [_HANDLE]),
     "mt_get": (C.c_int, [_HANDLE, C.c_int, C.c_void_p, C.c_int64, C.c_int]),

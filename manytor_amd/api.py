@@ -291,6 +291,26 @@ class Multienv:
         e = self._engine
         return (BatchView(e, L.F_OBS), BatchView(e, L.F_REWARD), BatchView(e, L.F_DONE, post=lambda a: a.astype(bool)))
 
+    def step_sequence(self, actions):
+        """T consecutive step()s with known actions -- (T, N, D) degrees: nested lists, an array or a device tensor -- in
+        ONE launch (StepEngine.rollout_actions) -> (obs2 of the LAST step, rewards, dones).  obs2 follows step()'s rule
+        (list of rows for small batches, else a BatchView); rewards / dones are T lists of N ints / bools for small
+        batches, else (T, N) numpy arrays.  Frames are not streamed to a viewer: intermediate poses are never stored."""
+        e = self._engine
+        if not (hasattr(actions, "is_cuda") and actions.is_cuda):
+            actions = np.asarray(actions)
+            if actions.ndim == 2:                              # a single step's (N, D)
+                actions = actions[None]
+        res = e.rollout_actions(actions, layout="env_major", log=True)
+        e.sync()
+        rew = res["reward"].cpu().numpy()
+        done = res["done"].cpu().numpy().astype(bool)
+        self._step_idx += int(rew.shape[0])
+        if self._materialize:
+            return ([row.astype(np.float64) for row in e.obs()], [[int(r) for r in row] for row in rew],
+                    [[bool(d) for d in row] for row in done])
+        return BatchView(e, L.F_OBS), rew, done
+
     def close(self):
         self._engine.close()
 

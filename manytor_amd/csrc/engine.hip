@@ -325,6 +325,18 @@ static void choose_dispatch(mt_handle h) {
     seen("MT_ROLLOUT_EARLY");
   }
 
+  // ---- mt_rollout_tape: the two optional choices of rollout_tape_kernel (kernels.h), off unless measured to pay ----
+  h->tape_prefetch = false;
+  if (env_int("MT_TAPE_PREFETCH", &v)) {
+    h->tape_prefetch = v != 0;
+    seen("MT_TAPE_PREFETCH");
+  }
+  h->tape_nt_loads = false;
+  if (env_int("MT_TAPE_NT", &v)) {
+    h->tape_nt_loads = v != 0;
+    seen("MT_TAPE_NT");
+  }
+
   if (h->custom_frames) h->lds_table = false;
   // The schedule of launches over `envs` envs, against the thresholds of their scope
   auto schedule_for = [&](int64_t envs, int64_t split4_max, int64_t split2_max, int64_t prefetch_other_max) {
@@ -728,6 +740,28 @@ void launch_rollout(mt_handle h, const StepArgs& a, int lanes, const RolloutArgs
   MT_DISPATCH_D(h->D, launch_rollout_d, h, a, lanes, r);
 }
 
+// rollout_tape_kernel on the whole batch: one env per lane for every table kind and batch size.
+template <class Tbl, bool PREFETCH>
+void launch_tape_t(mt_handle h, const StepArgs& a, const TapeArgs& r) {
+  const size_t lds = (size_t)3 * h->K * kBlock * sizeof(float);  // 21.5 KB at K = 7, 96 KB at K = 32
+  if (lds > 65536)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_tape_kernel<Tbl, PREFETCH>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((rollout_tape_kernel<Tbl, PREFETCH>), grid_for(a.n), dim3(kBlock), lds, h->stream, a, r);
+}
+template <int D>
+void launch_tape_d(mt_handle h, const StepArgs& a, const TapeArgs& r) {
+  launch_tape_t<RtTable<D>, false>(h, a, r);
+}
+// (the next-step prefetch exists for the compile-time tables, where it was measured: tools/tape_rollout_sweep.py)
+bool tape_prefetches(const mt_engine* h) { return h->tape_prefetch && h->static_kind != 0; }
+void launch_tape(mt_handle h, const StepArgs& a, const TapeArgs& r) {
+  const bool pf = tape_prefetches(h);
+  if (h->static_kind == 1) return pf ? launch_tape_t<Ref4Table, true>(h, a, r) : launch_tape_t<Ref4Table, false>(h, a, r);
+  if (h->static_kind == 2) return pf ? launch_tape_t<Dh7Table, true>(h, a, r) : launch_tape_t<Dh7Table, false>(h, a, r);
+  MT_DISPATCH_D(h->D, launch_tape_d, h, a, r);
+}
+
 // The rollout kernels implement the default trigonometry and the reference's frame rows only.
 bool fusable(mt_handle h) { return h->trig == 0 && !h->lds_table && !h->trace && !h->custom_frames; }
 
@@ -1104,6 +1138,9 @@ const char* mt_describe_dispatch(mt_handle h) {
       ",\"chains\":" + num(multi && !h->chains_forced ? 1 : h->chains) +
       ",\"absorbs_reset\":" + b(h->defer_reset && (multi || chained_rollout_absorbs_reset(h))) + ",\"writes_snapshot\":" + b(h->snap_in_rollout && (multi || (h->chains > 1 && !graph && !h->trace))) + "}" +
       ",\"fused\":{\"usable\":" + b(fusable(h)) + ",\"lanes_per_env\":" + num(h->sched[mt_engine::kBatch].rollout_lanes) + "}" +
+      // mt_rollout_tape: one form for every batch size (the lane-split and two-chain forms do not exist for it)
+      ",\"tape\":{\"usable\":" + b(fusable(h)) + ",\"lanes_per_env\":1,\"chains\":1,\"prefetch\":" + b(tape_prefetches(h)) +
+      ",\"nt_loads\":" + b(h->tape_nt_loads) + "}" +
       ",\"reset\":{\"lanes_per_env\":" + num(h->reset_split ? 4 : 1) + "}" +
       ",\"overrides\":\"" + h->overrides + "\"" +
       ",\"policy\":{\"step_split4_max\":" + num(P.step_split4_max) + ",\"step_split2_max\":" + num(P.step_split2_max) +
@@ -1865,6 +1902,59 @@ int mt_rollout_fused(mt_handle h, int n_steps, uint64_t seed, uint32_t step_idx0
   RolloutArgs r{n_steps, step_idx0, auto_reset ? 1u : 0u, h->cfg.radius, 0u, 0u, 0u, 0u, nullptr};
   launch_rollout(h, h->args, h->sched[mt_engine::kBatch].rollout_lanes, r);
   return check_launch(h, "rollout_kernel");
+}
+
+int mt_rollout_tape(mt_handle h, const mt_tape* tape) {
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  MT_REQUIRE(h, tape != nullptr, "tape is NULL");
+  MT_REQUIRE(h, tape->struct_size == (int32_t)sizeof(mt_tape), "mt_tape.struct_size does not match this library");
+  MT_REQUIRE(h, tape->reserved == 0, "mt_tape.reserved must be 0");
+  MT_REQUIRE(h, (tape->flags & ~(MT_TAPE_AUTO_RESET | MT_TAPE_DRY_RUN)) == 0, "unknown MT_TAPE_* flag");
+  const bool auto_reset = (tape->flags & MT_TAPE_AUTO_RESET) != 0, dry = (tape->flags & MT_TAPE_DRY_RUN) != 0;
+  MT_REQUIRE(h, !(auto_reset && dry), "MT_TAPE_DRY_RUN | MT_TAPE_AUTO_RESET: the re-arm writes the return ring");
+  MT_REQUIRE(h, tape->n_steps >= 0, "n_steps must be >= 0");
+  if (!fusable(h)) {  // the rollout kernels do not implement these
+    const char* what = h->custom_frames ? "custom obs_frame / ee_frame"
+                       : h->trace       ? "MT_FLAG_TRACE"
+                       : h->lds_table   ? "MT_FLAG_DH_IN_LDS"
+                       : h->trig == 2   ? "MT_FLAG_HW_TRIG"
+                       : (h->cfg.flags & MT_FLAG_DIRECT_TRIG) ? "MT_FLAG_DIRECT_TRIG"
+                       : h->trig == 1   ? "substeps beyond the recurrence's reach (per-pose trigonometry)"
+                                        : "a profiling flag (MT_FLAG_ABLATE_*)";
+    return fail(h, MT_ERR_UNSUPPORTED, std::string("mt_rollout_tape: not available on a handle with ") + what);
+  }
+  if (!h->is_reset) return fail(h, MT_ERR_STATE, "mt_rollout_tape before mt_reset / mt_reset_random");
+  if (tape->n_steps == 0) return MT_OK;
+  MT_REQUIRE(h, tape->actions != nullptr, "mt_tape.actions is NULL");
+  MT_REQUIRE(h, tape->ld >= h->n, "mt_tape.ld is smaller than n_envs");
+  MT_REQUIRE(h, !(tape->reward_log || tape->done_log) || tape->log_ld >= h->n, "mt_tape.log_ld is smaller than n_envs");
+  MT_ENTER(h);
+  if (auto_reset) {
+    h->args.seed_lo = (uint32_t)tape->seed;  // as mt_reset_done(seed) leaves them
+    h->args.seed_hi = (uint32_t)(tape->seed >> 32);
+    int rcg = order_behind_inplace_gather(h, h->stream);  // the in-kernel re-arm writes MT_F_LAST_RETURN
+    if (rcg) return rcg;
+  }
+  TapeArgs r{};
+  r.tape = tape->actions;
+  r.tape_ld = tape->ld;
+  r.reward_log = tape->reward_log;
+  r.done_log = tape->done_log;
+  r.log_ld = tape->log_ld;
+  r.return_out = tape->return_out;
+  r.T = tape->n_steps;
+  r.auto_reset = auto_reset ? 1u : 0u;
+  r.dry_run = dry ? 1u : 0u;
+  r.nt_loads = h->tape_nt_loads ? 1u : 0u;
+  r.seed_lo = (uint32_t)tape->seed;
+  r.seed_hi = (uint32_t)(tape->seed >> 32);
+  r.radius = h->cfg.radius;
+  launch_tape(h, h->args, r);
+  if (!dry) {
+    h->args.flags &= ~kFlagWholeGoals;  // tape angles are anybody's floats
+    h->codes_valid = false;             // the kernel writes targets as floats only
+  }
+  return check_launch(h, "rollout_tape_kernel");
 }
 
 int mt_observe(mt_handle h) {

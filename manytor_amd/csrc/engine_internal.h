@@ -117,6 +117,8 @@ struct mt_engine {
   uint32_t pend_episode = 0;
   bool snap_in_rollout = true;  // the last launch of an mt_rollout call also stores the returns to the gather's snapshot row
   bool snap_valid = false;      // ... it did, and nothing has touched the returns since: mt_gather_returns_begin skips its copy
+  bool tape_prefetch = false;   // mt_rollout_tape: the tape row of step s + 1 requested before the kinematics of step s (MT_TAPE_PREFETCH)
+  bool tape_nt_loads = false;   // ... and the tape read with non-temporal loads (MT_TAPE_NT)
   std::string overrides;        // the MT_* overrides choose_dispatch saw ("NAME=value,...")
   std::string describe;         // mt_describe_dispatch's text
   hipStream_t chain_streams[kMaxChains] = {nullptr, nullptr, nullptr, nullptr};  // [0] unused: chain 0 runs on `stream`

@@ -2143,6 +2143,178 @@ __global__ __launch_bounds__(kBlock) void rollout_split_kernel(const StepArgs a,
 }
 
 // ---------------------------------------------------------------------------
+// rollout driven by a device action tape (mt_rollout_tape): rollout_kernel with the second action source -- joint j of
+// env i at step s is tape[(s * D + j) * tape_ld + i], screened like step_kernel's staged action (unusable_angle: the env
+// holds its pose, the pair is counted) -- for callers that hold the next T actions of every env on the device (sampling
+// planners, replays, open-loop policy chunks).  Pose, alive mask and return stay in registers and the targets in LDS
+// ([3K][kBlock]) as in rollout_kernel; per step it runs the device functions step_kernel runs on the same inputs
+// (route_kinematics with no whole-degree assumption: TABLE = false, prev_whole = false; within_box; the dead-target
+// zeroing), so
+//   tape(T)  ==  T x (set_actions(row t); step)                 (auto_reset = 0)
+//   tape(T)  ==  T x (set_actions(row t); step; reset_done)     (auto_reset = 1, state fields)
+// bit for bit.  PoseCache is kept across steps: it holds sincos_deg(act + off) of the action just taken, which is the
+// very float and function the next step would evaluate for its start pose, fractional angles included.
+// What the intermediate steps skip: the observation arithmetic (observe_target) and every MT_F_* output store -- only
+// the LAST step of the call writes obs / reward / done / ee / zmin.  What every step writes: two log bytes (reward,
+// done), where asked for.  Per env-step: 4 D bytes of tape read + 2 bytes of logs; the state is read and written once
+// per call.
+//   dry_run  : nothing resident is written (arena, ring, bad-action counter): only the logs and return_out
+//   PREFETCH : the tape row of step s + 1 is requested before the kinematics of step s (D more live registers); else it is
+//              requested behind step s, once nothing else is live.  Instantiated for the compile-time tables only.
+//   nt_loads : the tape is read with non-temporal loads (it is read once)
+// One env per lane, one form for every batch size and table kind.
+// ---------------------------------------------------------------------------
+struct TapeArgs {
+  const float* tape;     // [T * D][tape_ld]
+  int64_t tape_ld;
+  int8_t* reward_log;    // [T][log_ld] or NULL
+  uint8_t* done_log;     // [T][log_ld] or NULL
+  int64_t log_ld;
+  float* return_out;     // [n] or NULL
+  int32_t T;
+  uint32_t auto_reset, dry_run, nt_loads;
+  uint32_t seed_lo, seed_hi;  // keys the targets of re-armed envs
+  float radius;
+};
+
+// a tape row element: read once, so optionally non-temporal (wave-uniform choice)
+template <bool R>
+__device__ __forceinline__ float tape_load(const float* row, LaneOffset<R>& o, bool nt) {
+  global_ptr<const float> p = (global_ptr<const float>)(uniform_row(row) + lane_offset(o));
+  return nt ? __builtin_nontemporal_load(p) : *p;
+}
+
+template <class Tbl, bool PREFETCH = false>
+__global__ __launch_bounds__(kBlock) void rollout_tape_kernel(const StepArgs a, const TapeArgs r) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];  // [3K][kBlock]
+  constexpr int D = Tbl::D;
+  const Tbl t = TableMaker<Tbl>::make(a.dh);
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  LaneOffset<true> o4{i * 4u}, o1{i};
+  if (i >= a.n) return;  // (no block barrier and no wave-cooperative draw below)
+  const int64_t ld = a.ld;
+  const uint64_t seed = ((uint64_t)r.seed_hi << 32) | r.seed_lo;
+  const uint64_t env_id = (uint64_t)(a.env_base + i);
+  float* col = tile + threadIdx.x;
+  const bool commit = r.dry_run == 0;  // (wave-uniform: a launch argument)
+  const bool nt = r.nt_loads != 0;
+
+  const uint32_t all_alive = (a.K >= 32) ? 0xFFFFFFFFu : ((1u << a.K) - 1u);
+  float g[D], cur[D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) cur[j] = tape_load(r.tape + (int64_t)j * r.tape_ld, o4, nt);
+#pragma unroll
+  for (int j = 0; j < D; ++j) g[j] = ldr(a.goals + j * ld, o4);
+  uint32_t am = ldr(a.alive, o4);
+  float total = ldr(a.total_reward, o4);
+  uint32_t episode = r.auto_reset ? ldr(a.episodes, o4) : 0u;
+  for (int k = 0; k < 3 * a.K; ++k) col[k * kBlock] = ldr(a.points + (int64_t)k * ld, o4);
+  bool ended = false, dirty = false;
+  float ret = 0.f;  // sum of this call's rewards, across re-arms
+  PoseCache<D> pose;
+  bool pose_valid = false;  // nothing known about the pose loaded from memory
+
+  for (int s = 0; s < r.T; ++s) {
+    const bool last = s == r.T - 1;  // (wave-uniform)
+    float act[D], raw[D], el[3], e[3];
+#pragma unroll
+    for (int j = 0; j < D; ++j) raw[j] = cur[j];
+    if (PREFETCH && !last) {
+#pragma unroll
+      for (int j = 0; j < D; ++j) cur[j] = tape_load(r.tape + ((int64_t)(s + 1) * D + j) * r.tape_ld, o4, nt);
+    }
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < D; ++j) bad |= unusable_angle(raw[j]);
+#pragma unroll
+    for (int j = 0; j < D; ++j) act[j] = bad ? g[j] : raw[j];  // the env holds its pose this step
+    if (bad && commit) atomicAdd(a.bad_actions, 1u);          // ... and the pair is counted (mt_bad_action_count)
+
+    const float zmin = route_kinematics<Tbl, 0, true, false>(t, a.S, a.inv_sm1, g, act, el, e, &pose, pose_valid, nullptr, false);
+    pose_valid = true;
+    const bool ground = zmin < 0.f;
+    const bool out = last && commit;  // the step whose outputs MT_F_* keep
+    if (out && a.zmin) str_stream(a.zmin, o4, zmin);
+
+    uint32_t nam = am;
+    for (int k = 0; k < a.K; ++k) {
+      float* pk = col + 3 * k * kBlock;
+      const float x = pk[0], y = pk[kBlock], z = pk[2 * kBlock];
+      const bool al = (am >> k) & 1u;
+      float dist = 0.f, rr = 0.f, th = 0.f;
+      if (al) {
+        if (out) observe_target(el, x, y, z, dist, rr, th);
+        if (within_box(e, x, y, z, a.tol)) nam &= ~(1u << k);
+      } else if ((x != 0.f) | (y != 0.f) | (z != 0.f)) {  // manytor.py:148
+        pk[0] = 0.f;
+        pk[kBlock] = 0.f;
+        pk[2 * kBlock] = 0.f;
+        dirty = true;
+      }
+      if (out) {
+        float* orow = a.obs + (int64_t)(3 * k) * ld;
+        str_stream(orow, o4, dist);
+        str_stream(orow + ld, o4, rr);
+        str_stream(orow + 2 * ld, o4, th);
+      }
+    }
+    const int32_t rew = ground ? -1 : ((nam != am) ? 1 : 0);
+    bool done = (nam == 0u);
+    if (a.flags & MT_FLAG_TERMINATE_ON_GROUND) done |= ground;
+    total += (float)rew;
+    ret += (float)rew;
+    am = nam;
+#pragma unroll
+    for (int j = 0; j < D; ++j) g[j] = act[j];
+    if (r.reward_log) str_stream(r.reward_log + (int64_t)s * r.log_ld, o1, (int8_t)rew);
+    if (r.done_log) str_stream(r.done_log + (int64_t)s * r.log_ld, o1, (uint8_t)(done ? 1 : 0));
+    if (out) {
+#pragma unroll
+      for (int j = 0; j < D; ++j) str(a.actions + j * ld, o4, raw[j]);  // what mt_set_actions(row T - 1) would have left
+#pragma unroll
+      for (int q = 0; q < 3; ++q) str_stream(a.ee + q * ld, o4, e[q]);
+      str_stream(a.reward, o4, rew);
+      // 2 = "finished in this step and already re-armed below" (see rollout_kernel)
+      str_stream(a.done, o1, (uint8_t)(done ? (r.auto_reset ? 2 : 1) : 0));
+      const unsigned long long bits = __ballot(done);
+      if ((threadIdx.x & 63) == 0) a.done_bits[i >> 6] = bits;
+    }
+
+    if (done && r.auto_reset) {  // re-arm, as in rollout_kernel (never in a dry run: the host refuses the combination)
+      record_finished(a, i, episode, total);
+      ended = true;
+      total = 0.f;
+      am = all_alive;
+      episode += 1u;
+#pragma unroll
+      for (int j = 0; j < D; ++j) g[j] = 0.f;
+      pose_valid = false;
+      draw_targets(seed, env_id, episode, a.K, r.radius, [&](int k, float x, float y, float z) {
+        float* pk = col + 3 * k * kBlock;
+        pk[0] = x;
+        pk[kBlock] = y;
+        pk[2 * kBlock] = z;
+      });
+      dirty = true;
+    }
+    if (!PREFETCH && !last) {
+#pragma unroll
+      for (int j = 0; j < D; ++j) cur[j] = tape_load(r.tape + ((int64_t)(s + 1) * D + j) * r.tape_ld, o4, nt);
+    }
+  }
+
+  if (r.return_out) str_stream(r.return_out, o4, ret);
+  if (!commit) return;
+#pragma unroll
+  for (int j = 0; j < D; ++j) str(a.goals + j * ld, o4, g[j]);
+  str(a.alive, o4, am);
+  str(a.total_reward, o4, total);
+  if (ended) str(a.episodes, o4, episode);
+  if (dirty)
+    for (int k = 0; k < 3 * a.K; ++k) str(a.points + (int64_t)k * ld, o4, col[k * kBlock]);
+}
+
+// ---------------------------------------------------------------------------
 // get_observations() at the current pose (manytor.py:141-153).
 // ---------------------------------------------------------------------------
 template <int D>

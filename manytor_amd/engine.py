@@ -152,6 +152,7 @@ class StepEngine:
             self._call(self._lib.mt_use_own_stream)
         else:
             self._call(self._lib.mt_set_stream, C.c_void_p(int(hip_stream)))
+        self._caller_stream = None if hip_stream is None else int(hip_stream)
 
     def use_torch_stream(self):
         """Launch on torch's current stream of this device: torch ops on that stream (device_tensor views, RCCL
@@ -346,6 +347,81 @@ class StepEngine:
         self._call(self._lib.mt_rollout_fused, int(n_steps), C.c_uint64(seed), C.c_uint32(step_idx0),
                    1 if auto_reset else 0)
         self.version += 1
+
+    def _tape_tensor(self, actions, layout):
+        """(tensor, ld) of a device action tape in the kernel's layout: f32, joint j of env i at step t at
+        [(t * D + j) * ld + i].  A CUDA f32 (T, D, N) tensor with unit env stride and a uniform row pitch >= N goes in
+        zero-copy; anything else becomes a contiguous (T, D, N) f32 tensor on the engine's device."""
+        import torch
+        n, d = self.n_envs, self.dof
+        if layout not in ("env_major", "soa"):
+            raise ValueError("layout must be 'env_major' (T, N, D) or 'soa' (T, D, N)")
+        dev = torch.device("cuda", self.device)
+        if _is_torch_tensor(actions):
+            t = actions.detach()
+        else:
+            a = np.asarray(actions)
+            if a.dtype not in _ACTION_DT:
+                a = a.astype(np.float64)
+            a = np.ascontiguousarray(a)
+            t = torch.from_numpy(a if a.flags.writeable else a.copy())
+        if t.dim() != 3 or tuple(t.shape[1:]) != ((d, n) if layout == "soa" else (n, d)):
+            want = f"(T, {d}, {n})" if layout == "soa" else f"(T, {n}, {d})"
+            raise ValueError(f"actions must be {want} for layout={layout!r}, got {tuple(t.shape)}")
+        if t.shape[0] == 0:
+            return torch.empty((0, d, n), dtype=torch.float32, device=dev), n
+        if (layout == "soa" and t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.stride(2) == 1
+                and t.stride(1) >= n and t.stride(0) == d * t.stride(1)):
+            return t, int(t.stride(1))
+        t = t.to(device=dev, dtype=torch.float32)
+        if layout == "env_major":
+            t = t.permute(0, 2, 1)
+        return t.contiguous(), n
+
+    def rollout_actions(self, actions, *, layout="env_major", auto_reset=False, seed=0x5EED, log=False, returns=False,
+                        dry_run=False):
+        """T steps with the caller's actions in ONE launch (mt_rollout_tape): `actions` is (T, N, D) degrees
+        (layout="env_major") or (T, D, N) (layout="soa"; a CUDA float32 tensor of that layout is read in place).  Behaves
+        as T x (set_actions(actions[t]); step()), with auto_reset as T x (...; reset_done(seed)); the fields hold the
+        state after T steps and the outputs of the last one.  log=True also returns the per-step `reward` (T, N) int8 and
+        `done` (T, N) uint8, returns=True the per-env sum of the call's rewards `returns` (N,) float32 -- device tensors
+        in a dict (None when neither is asked for).  dry_run=True evaluates only: nothing resident changes.
+        On torch's stream (use_torch_stream) the call is ordered with the torch ops around it and waits for nothing;
+        on the engine's own stream it waits for torch's current stream before and for its own launch after."""
+        import torch
+        if auto_reset and dry_run:
+            raise ValueError("dry_run and auto_reset exclude each other: the re-arm writes the return ring")
+        tape, ld = self._tape_tensor(actions, layout)
+        T, n = int(tape.shape[0]), self.n_envs
+        dev = tape.device
+        out = {}
+        if log:
+            out["reward"] = torch.empty((T, n), dtype=torch.int8, device=dev)
+            out["done"] = torch.empty((T, n), dtype=torch.uint8, device=dev)
+        if returns:
+            out["returns"] = torch.zeros(n, dtype=torch.float32, device=dev)
+        arg = L.MtTape()
+        arg.struct_size = C.sizeof(L.MtTape)
+        arg.n_steps = T
+        arg.actions = tape.data_ptr() if T else None
+        arg.ld = ld
+        arg.reward_log = out["reward"].data_ptr() if log and T else None
+        arg.done_log = out["done"].data_ptr() if log and T else None
+        arg.log_ld = n
+        arg.return_out = out["returns"].data_ptr() if returns else None
+        arg.seed = int(seed)
+        arg.flags = (L.TAPE_AUTO_RESET if auto_reset else 0) | (L.TAPE_DRY_RUN if dry_run else 0)
+        arg.reserved = 0
+        cur = int(torch.cuda.current_stream(self.device).cuda_stream)
+        ordered = getattr(self, "_caller_stream", None) == cur   # the engine launches on torch's current stream
+        if not ordered:
+            torch.cuda.current_stream(self.device).synchronize()
+        self._call(self._lib.mt_rollout_tape, C.byref(arg))
+        if not ordered:
+            self.sync()     # the tape and the outputs are torch's memory: done with before torch may reuse or read it
+        if not dry_run:
+            self.version += 1
+        return out or None
 
     def observe(self):
         """Environment.get_observations (manytor.py:141-153); result in field OBS."""
