@@ -39,6 +39,11 @@ def _table(m, name):
         return m.REF_DH_TABLE, 51.3
     if name == "dh7":
         return m.DH7_TABLE, 92.6
+    if name.startswith("dof"):               # "dof3": a runtime table of that many joints, test_gpu_parity.py's recipe
+        dof = int(name[3:])
+        rng = np.random.RandomState(dof)
+        return np.column_stack([rng.uniform(0, 10, dof), rng.choice([-np.pi / 2, 0, np.pi / 2, 0.4], dof),
+                                rng.uniform(2, 15, dof), rng.choice([0, -np.pi / 2, 0.25], dof)]), 40.0
     return sp.fractional_offset_table()      # "rt5": runtime table, theta offsets that are no whole degrees
 
 
@@ -147,24 +152,32 @@ def unusable(row):
     return (~np.isfinite(row) | (np.abs(row) > np.float32(32768.0))).any(axis=1)
 
 
-def run_tape_against_oracle(m, table_name, n, k, T, tol, auto_reset, tape):
-    """One committing rollout_actions call on the GPU vs T oracle steps on the host; returns what the callers assert on."""
+def run_tape_against_oracle(m, table_name, n, k, T, tol, auto_reset, tape, substeps=25, terminate_on_ground=False,
+                            specialize=True, episode0=0, start_pose=None):
+    """One committing rollout_actions call on the GPU vs T oracle steps on the host; returns what the callers assert on.
+    episode0: the full reset in front of the call is reset_random(SEED, episode0).  start_pose: fp32 (n, D) joint angles
+    written with eng.set(MT_F_GOALS) behind that reset.  terminate_on_ground: the oracle has no such flag; the episode of an
+    env that touched the ground (reward == -1) ends here, ahead of the re-arm and of the comparison of the done log."""
     from oracle import c_oracle
     from oracle import philox_ref as px
     table, radius = _table(m, table_name)
-    eng = make_engine(m, table_name, n, k, tol)
-    ora = c_oracle.COracle(n, k, table=np.asarray(table), radius=radius, pickup_tol=tol, threads=16)
+    eng = make_engine(m, table_name, n, k, tol, substeps=substeps, terminate_on_ground=terminate_on_ground, specialize=specialize)
+    ora = c_oracle.COracle(n, k, table=np.asarray(table), substeps=substeps, radius=radius, pickup_tol=tol, threads=16)
     ids = np.arange(n, dtype=np.uint64)
-    eng.reset_random(SEED, 0)
+    eng.reset_random(SEED, episode0)
     ora.reset(eng.points().astype(np.float64))
+    if start_pose is not None:
+        eng.set(m.lib.F_GOALS, start_pose)
+        ora.goals[:] = start_pose.astype(np.float64)
     res = eng.rollout_actions(tape, auto_reset=auto_reset, seed=SEED, log=True, returns=True)      # ONE launch
     eng.sync()
     rew_log, done_log = res["reward"].cpu().numpy(), res["done"].cpu().numpy()
 
     clean = np.ones(n, dtype=bool)
-    episodes = np.zeros(n, dtype=np.int64)
+    episodes = np.full(n, episode0, dtype=np.int64)
     last_ret = np.zeros(n)
     ring = np.zeros((n, RING))
+    written = np.zeros((n, RING), dtype=bool)                      # slots an env has actually written
     ret = np.zeros(n)
     held = 0
     last = None
@@ -174,6 +187,8 @@ def run_tape_against_oracle(m, table_name, n, k, T, tol, auto_reset, tape):
         act = np.where(bad[:, None], ora.goals, tape[t].astype(np.float64))     # an unusable action: the pose is held
         pre_alive = ora.alives.copy()
         obs_ref, rew_ref, done_ref = ora.step(act)
+        if terminate_on_ground:
+            done_ref = done_ref | (rew_ref == -1)
         pm = np.where(pre_alive, ora.pickup_margin, np.inf).min(axis=1)
         clean &= ~((ora.ground_margin < GUARD) | (pm < GUARD))
         ret += rew_ref
@@ -185,7 +200,9 @@ def run_tape_against_oracle(m, table_name, n, k, T, tol, auto_reset, tape):
                         points=ora.points.copy(), zmin=ora.zmin.copy())
         if auto_reset and done_ref.any():                          # what the kernel does in the step an env finishes
             idx = np.flatnonzero(done_ref)
-            ring[idx, episodes[idx] % RING] = ora.total_reward[idx]
+            slot = (episodes[idx] - episode0) % RING               # include/manytor_hip.h: MT_F_RETURN_RING
+            ring[idx, slot] = ora.total_reward[idx]
+            written[idx, slot] = True
             last_ret[idx] = ora.total_reward[idx]
             episodes[idx] += 1
             ora.goals[idx] = 0.0
@@ -194,8 +211,11 @@ def run_tape_against_oracle(m, table_name, n, k, T, tol, auto_reset, tape):
             ora.points[idx] = px.sample_targets(SEED, ids[idx], episodes[idx], k, radius).astype(np.float64)
 
     c = clean
-    print(f"[tape-vs-oracle] {table_name} n={n} K={k} T={T} tol={tol} auto_reset={auto_reset}: clean share {c.mean():.4f}, "
-          f"re-arms {int(episodes.sum())}, max episodes {int(episodes.max())}, held env-steps {held}")
+    finished = episodes - episode0
+    print(f"[tape-vs-oracle] {table_name} n={n} K={k} T={T} tol={tol} auto_reset={auto_reset} S={substeps} "
+          f"terminate={terminate_on_ground} specialize={specialize} episode0={episode0} "
+          f"start_pose={'no' if start_pose is None else 'yes'}: clean share {c.mean():.4f}, "
+          f"re-arms {int(finished.sum())}, max episodes {int(finished.max())}, held env-steps {held}")
     assert c.mean() >= MIN_CLEAN, c.mean()
     np.testing.assert_array_equal(eng.goals()[c], ora.goals[c].astype(np.float32))
     np.testing.assert_array_equal(eng.alives()[c], ora.alives[c])
@@ -204,12 +224,10 @@ def run_tape_against_oracle(m, table_name, n, k, T, tol, auto_reset, tape):
     np.testing.assert_array_equal(eng.episodes()[c], episodes[c])
     np.testing.assert_array_equal(res["returns"].cpu().numpy()[c], ret[c].astype(np.float32))
     if auto_reset:
-        fin = c & (episodes > 0)
+        fin = c & (finished > 0)
         np.testing.assert_array_equal(eng.last_return()[fin], last_ret[fin].astype(np.float32))
-        got = eng.return_ring()
-        for e in range(1, RING + 1):                               # slots an env has actually written
-            sel = c & (episodes >= e)
-            np.testing.assert_array_equal(got[sel, e - 1], ring[sel, e - 1].astype(np.float32))
+        sel = written & c[:, None]
+        np.testing.assert_array_equal(eng.return_ring()[sel], ring[sel].astype(np.float32))
     np.testing.assert_array_equal(eng.reward()[c], last["rew"][c])
     done_raw = eng.get(m.lib.F_DONE)
     np.testing.assert_array_equal(done_raw[c] != 0, last["done"][c])
@@ -218,7 +236,8 @@ def run_tape_against_oracle(m, table_name, n, k, T, tol, auto_reset, tape):
     assert_obs_close(eng.obs()[c], last["obs"][c], last["jc"][c, -2], last["points"][c], last["pre_alive"][c])
     assert np.abs(eng.zmin() - last["zmin"])[c].max() <= GUARD
     assert eng.bad_action_count() == held
-    return dict(eng=eng, clean=c, episodes=episodes, finished=int((episodes > 0).sum()), max_episodes=int(episodes.max()))
+    return dict(eng=eng, clean=c, episodes=finished, finished=int((finished > 0).sum()), max_episodes=int(finished.max()),
+                rearms=int(finished.sum()), ring_written=int((written & c[:, None]).sum()))
 
 
 @pytest.mark.parametrize("table_name,n,k,T,tol,auto_reset,kind", [

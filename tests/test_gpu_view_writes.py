@@ -24,6 +24,8 @@ exact outside the guard band.  One exception to "every env" for the z-minimum, s
 comparison and not of the kernels: inside mt_rollout_fused(auto_reset) an env whose pickup decision sat in the guard band
 may have been re-armed (pose zeroed) on one side only, and the NEXT step's route then starts from different poses; such
 envs are left out of that call's z-minimum (their end effector, which depends on the action alone, is still compared)."""
+import copy
+
 import numpy as np
 import pytest
 
@@ -110,6 +112,10 @@ class Mirror:
         self.risky = np.zeros(n, dtype=bool)                # envs that touched the guard band since the last checkpoint
         self.zmin_free = np.zeros(n, dtype=bool)            # ... in a re-arming call, ahead of its last step (module docstring)
         self.stats = dict(env_steps=0, guarded=0, picked=0, grounded=0, airborne=0, dones=0)
+        self.tapes = []                                     # fp32 (T, n, D) action tapes, uploaded before the replay
+        self.tape_calls = []                                # tape calls since the last checkpoint: their expected logs
+        self.tape_pairs = []                                # ... and pairs of them whose logs must be the same bits
+        self.bad_actions = 0                                # (env, step) pairs a committing tape call held
         self._full_reset(0)
 
     # ---- state transitions -------------------------------------------------------------------
@@ -228,6 +234,70 @@ class Mirror:
     def take_views(self, *fields):
         self.program.append(("views", fields))
 
+    # ---- mt_rollout_tape ---------------------------------------------------------------------------
+    _MIRRORED = ("episode0", "episodes", "last_return", "ring", "ring_known", "done", "reward", "last", "risky", "zmin_free",
+                 "stats", "bad_actions")
+    _ORACLE = ("goals", "points", "alive_u8", "total_reward", "joints_coordinates", "ground_margin", "pickup_margin",
+               "ground_hit", "zmin")
+
+    def rollout_actions(self, tape32, auto_reset=False, dry_run=False, compare_resident=True):
+        """eng.rollout_actions(tape, log=True, returns=True) on an fp32 (T, n, D) tape: T oracle steps, an unusable angle
+        (kernels.h: unusable_angle) holds the pose, finished envs are re-armed as _rearm does, only the last row leaves
+        outputs.  The logs and `returns` are compared at the next checkpoint, for the envs outside the guard band.  A dry
+        run plays the same steps for its logs and puts the oracle back; on the GPU everything resident is compared bit for bit
+        with a host snapshot taken in front of the call (compare_resident=False: no snapshot, hence no host wait in front of
+        the call).  Returns the call's record (for expect_same_logs)."""
+        tape32 = np.ascontiguousarray(tape32, dtype=np.float32)
+        assert tape32.shape[1:] == (self.n, self.dof) and not (auto_reset and dry_run)
+        T = tape32.shape[0]
+        keep = None
+        if dry_run:
+            keep = ({f: copy.deepcopy(getattr(self, f)) for f in self._MIRRORED},
+                    {f: getattr(self.ora, f).copy() for f in self._ORACLE})
+        rew, done, held = [], [], 0
+        for t in range(T):
+            bad = (~np.isfinite(tape32[t]) | (np.abs(tape32[t]) > sp.LIMIT)).any(axis=1)
+            held += int(bad.sum())
+            self._step(np.where(bad[:, None], self.ora.goals, tape32[t].astype(np.float64)), rearm=auto_reset,
+                       last_of_call=t == T - 1)
+            rew.append(self.reward.copy())
+            done.append(self.done != 0)
+        call = dict(slot=len(self.tapes), T=T, auto_reset=auto_reset, dry=dry_run, compare_resident=compare_resident,
+                    reward=np.stack(rew).astype(np.int8), done=np.stack(done).astype(np.uint8),
+                    returns=np.stack(rew).sum(axis=0).astype(np.float32), risky=self.risky.copy(), res=None)
+        if dry_run:
+            for f, v in keep[0].items():
+                setattr(self, f, v)
+            for f, v in keep[1].items():
+                setattr(self.ora, f, v)
+        else:
+            self.bad_actions += held
+        self.tapes.append(tape32)
+        self.tape_calls.append(call)
+        self.program.append(("tape", call))
+        return call
+
+    def expect_same_logs(self, a, b):
+        """The logs and returns of two tape calls (a dry run and the committing call of the same rows): the same bits."""
+        self.tape_pairs.append((a, b))
+
+    def _return_row(self, field):
+        return dict(F_TOTAL_REWARD=self.ora.total_reward, F_LAST_RETURN=self.last_return)[field].astype(np.float32)
+
+    def gather_begin(self, key, field="F_TOTAL_REWARD", snapshot=True):
+        """eng.gather_begin of a return row (snapshot=False: the exchange reads the row in place).  The buffer must hold the
+        row as it is NOW; the envs that are in the guard band now are left out."""
+        self.program.append(("gather_begin", key, field, snapshot, self._return_row(field), self.risky.copy()))
+
+    def gather_end(self, key, stale=None, must_differ=0.1):
+        """gather_wait(host) of gather_begin(key).  `stale` is what a wrong order would ship -- the row at another time, by
+        default as it is now, behind the calls queued since gather_begin -- and has to differ from the expected row in at
+        least `must_differ` of the envs, so that order is really what the comparison decides."""
+        begin = next(op for op in reversed(self.program) if op[0] == "gather_begin" and op[1] == key)
+        stale = self._return_row(begin[2]) if stale is None else np.asarray(stale, dtype=np.float32)
+        assert (stale != begin[4]).mean() > must_differ, (stale != begin[4]).mean()
+        self.program.append(("gather_end", key, stale))
+
     # ---- torch writes through the views --------------------------------------------------------
     def edit(self, field, rows32, rows=None):
         """view[:rows] = rows32 (an fp32 array in the view's (rows, n) orientation)."""
@@ -290,6 +360,9 @@ class Mirror:
     # ---- checkpoints -----------------------------------------------------------------------------
     def check(self, what="step", label=""):
         o = self.ora
+        if self.tape_calls:                                  # the logs of the tape calls since the last checkpoint come first
+            self.program.append(("tape_logs", self.tape_calls, self.tape_pairs, self.risky.copy(), self.bad_actions, label))
+            self.tape_calls, self.tape_pairs = [], []
         exp = dict(what=what, label=label, ok=~self.risky, zmin_ok=~self.zmin_free,
                    goals=o.goals.astype(np.float32), points=o.points.astype(np.float32), alive=o.alives.copy(),
                    total=o.total_reward.astype(np.float32), episodes=self.episodes.copy(),
@@ -348,7 +421,9 @@ def replay(m, eng, mir, on_torch_stream):
     import torch
     dev = f"cuda:{eng.device}"
     up = [torch.from_numpy(a).to(dev) for a in mir.uploads]
+    tapes = [torch.from_numpy(a).to(dev) for a in mir.tapes]
     views = {}
+    gathers = {}
     torch.cuda.synchronize()
     gathered = 0
     for op in mir.program:
@@ -386,11 +461,61 @@ def replay(m, eng, mir, on_torch_stream):
                 np.testing.assert_array_equal(got[ok], want[ok], err_msg=f"gather {gathered} ({how}): {stale} of {int(ok.sum())} envs "
                                               "hold the returns from before the torch write")
             gathered += 1
+        elif kind == "tape":
+            _tape_call(m, eng, op[1], tapes)
+        elif kind == "tape_logs":
+            eng.sync()
+            torch.cuda.synchronize()
+            _check_tape_logs(eng, *op[1:])
+        elif kind == "gather_begin":
+            _, key, field, snapshot, want, risky = op
+            gathers[key] = (eng.gather_begin(field=getattr(m.lib, field), snapshot=snapshot), want, ~risky)
+        elif kind == "gather_end":
+            buf, want, ok = gathers.pop(op[1])
+            eng.gather_wait(host=True)
+            got, stale = buf.cpu().numpy(), op[2]
+            n_stale = int(((got == stale) & (got != want))[ok].sum())
+            np.testing.assert_array_equal(got[ok], want[ok], err_msg=f"gather {op[1]}: {n_stale} of {int(ok.sum())} envs hold "
+                                          "the row of another moment")
         elif kind == "check":
             _checkpoint(m, eng, op[1])
         else:
             raise AssertionError(kind)
+    assert not mir.tape_calls and not gathers                # (a script ends with a checkpoint behind its last tape call)
     torch.cuda.synchronize()
+
+
+RESIDENT = ("F_ACTIONS", "F_GOALS", "F_POINTS", "F_ALIVE", "F_TOTAL_REWARD", "F_EPISODES", "F_LAST_RETURN", "F_RETURN_RING",
+            "F_OBS", "F_REWARD", "F_DONE", "F_DONE_BITS", "F_EE", "F_ZMIN")
+
+
+def _tape_call(m, eng, call, tapes):
+    """One tape call of the program.  The committing call waits for nothing beyond what eng.rollout_actions itself does."""
+    before = None
+    if call["dry"] and call["compare_resident"]:
+        eng.sync()
+        before = {f: eng.get(getattr(m.lib, f)) for f in RESIDENT}, eng.bad_action_count(), eng.version
+    call["res"] = eng.rollout_actions(tapes[call["slot"]], auto_reset=call["auto_reset"], seed=SEED, log=True, returns=True,
+                                      dry_run=call["dry"])
+    if before is not None:
+        eng.sync()
+        for f, v in before[0].items():
+            np.testing.assert_array_equal(eng.get(getattr(m.lib, f)), v, err_msg=f"{f} after a dry run")
+        assert (eng.bad_action_count(), eng.version) == before[1:]
+
+
+def _check_tape_logs(eng, calls, pairs, risky, bad_actions, tag):
+    for c in calls:
+        ok = ~(risky | c["risky"])
+        got = {key: c["res"][key].cpu().numpy() for key in ("reward", "done", "returns")}
+        assert got["reward"].dtype == np.int8 and got["done"].dtype == np.uint8 and got["reward"].shape == (c["T"], ok.size)
+        for key in ("reward", "done"):
+            np.testing.assert_array_equal(got[key][:, ok], c[key][:, ok], err_msg=f"{tag}: {key} log of tape call {c['slot']}")
+        np.testing.assert_array_equal(got["returns"][ok], c["returns"][ok], err_msg=f"{tag}: returns of tape call {c['slot']}")
+    for a, b in pairs:
+        for key in ("reward", "done", "returns"):
+            np.testing.assert_array_equal(a["res"][key].cpu().numpy(), b["res"][key].cpu().numpy(), err_msg=f"{tag}: {key}")
+    assert eng.bad_action_count() == bad_actions, tag
 
 
 def _assert_exercised(mir, k):
