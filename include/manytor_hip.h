@@ -40,7 +40,7 @@ extern "C" {
 #define MT_API
 #endif
 
-#define MT_VERSION 400          /* major*10000 + minor*100 + patch */
+#define MT_VERSION 410          /* major*10000 + minor*100 + patch */
 #define MT_MAX_DOF 8
 #define MT_MAX_TARGETS 32
 #define MT_MAX_RETURN_RING 64
@@ -273,6 +273,37 @@ typedef struct mt_tape {
   uint32_t reserved;        /* must be 0 */
 } mt_tape;
 MT_API int mt_rollout_tape(mt_handle h, const mt_tape* tape);
+
+/* A sampling planner's round in one call: score C candidate tapes per env from the SAME resident state, name each env's
+ * best, and (commit_steps = H > 0) execute the first H steps of that best plan for real.
+ * Evaluation: returns_out[c*ret_ld + i] is what mt_rollout_tape(MT_TAPE_DRY_RUN, actions = plane c, the same ld) writes to
+ * return_out[i], bit for bit; best_out[i] is the SMALLEST c whose return is maximal (numpy's argmax), best_return_out[i]
+ * that return.  The state is read once for all candidates, the selection happens on the device, nothing resident changes
+ * and unusable actions (see mt_rollout_tape) hold the pose without being counted.
+ * Commit: afterwards the handle is in the state mt_rollout_tape leaves for n_steps = H, the same seed, MT_TAPE_AUTO_RESET
+ * iff MT_SHOOT_AUTO_RESET, and the gathered tape chosen[(t*D + j)*ld + i] = actions[best_out[i]*cand_stride + (t*D + j)*ld + i]
+ * -- every field, the logs, return_out and mt_bad_action_count (the H committed steps of the chosen plane, once each).
+ * At most two launches on the handle's stream (evaluate + select, commit), no allocation, no host wait: legal under
+ * stream capture.  MT_ERR_UNSUPPORTED / MT_ERR_STATE as mt_rollout_tape; n_steps == 0 is a no-op. */
+#define MT_SHOOT_AUTO_RESET 0x1u  /* the committed steps re-arm finished envs, as MT_TAPE_AUTO_RESET */
+struct mt_shoot {          /* the struct and the call share the name, so the type is always written `struct mt_shoot` */
+  int32_t struct_size;     /* = sizeof(struct mt_shoot), checked */
+  int32_t n_steps;         /* T >= 0: horizon every candidate is scored over */
+  int32_t n_candidates;    /* C, 1..64 */
+  int32_t commit_steps;    /* H, 0..T: 0 = evaluate only; else execute steps 0..H-1 of each env's best plan for real */
+  const float* actions;    /* DEVICE f32 degrees: candidate c, step t, joint j, env i = actions[c*cand_stride + (t*D + j)*ld + i] */
+  int64_t ld;              /* >= n_envs */
+  int64_t cand_stride;     /* elements between candidates, >= T*D*ld */
+  float* returns_out;      /* DEVICE or NULL: (C, ret_ld) return of every candidate */
+  int64_t ret_ld;          /* >= n_envs when returns_out is given */
+  int32_t* best_out;       /* DEVICE (N,): index of each env's best candidate; required when commit_steps > 0, else optional */
+  float* best_return_out;  /* DEVICE or NULL (N,): that candidate's return over the T steps */
+  int8_t* reward_log; uint8_t* done_log; int64_t log_ld;   /* (H, log_ld) logs of the COMMITTED steps, as in mt_tape */
+  float* return_out;       /* DEVICE or NULL (N,): sum of the H committed rewards (across re-arms) */
+  uint64_t seed;           /* keys re-armed envs' targets (MT_SHOOT_AUTO_RESET) */
+  uint32_t flags, reserved;
+};
+MT_API int mt_shoot(mt_handle h, const struct mt_shoot* s);
 
 /* Environment.get_observations(), manytor.py:141-153, at the current pose (also
  * zeroes the coordinates of dead targets, :148).  Result in MT_F_OBS. */

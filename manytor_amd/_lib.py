@@ -97,6 +97,33 @@ class MtTape(C.Structure):
 TAPE_AUTO_RESET = 0x1
 TAPE_DRY_RUN = 0x2
 
+
+class MtShoot(C.Structure):
+    """mt_shoot of include/manytor_hip.h: the argument block of mt_shoot."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_steps", C.c_int32),
+        ("n_candidates", C.c_int32),
+        ("commit_steps", C.c_int32),
+        ("actions", C.c_void_p),
+        ("ld", C.c_int64),
+        ("cand_stride", C.c_int64),
+        ("returns_out", C.c_void_p),
+        ("ret_ld", C.c_int64),
+        ("best_out", C.c_void_p),
+        ("best_return_out", C.c_void_p),
+        ("reward_log", C.c_void_p),
+        ("done_log", C.c_void_p),
+        ("log_ld", C.c_int64),
+        ("return_out", C.c_void_p),
+        ("seed", C.c_uint64),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+SHOOT_AUTO_RESET = 0x1
+
 _HANDLE = C.c_void_p
 
 # name -> (restype, argtypes); exactly the prototypes of include/manytor_hip.h
@@ -126,6 +153,7 @@ PROTOTYPES = {
     "mt_rollout": (C.c_int, [_HANDLE, C.c_int, C.c_uint64, C.c_uint32]),
     "mt_rollout_fused": (C.c_int, [_HANDLE, C.c_int, C.c_uint64, C.c_uint32, C.c_int]),
     "mt_rollout_tape": (C.c_int, [_HANDLE, C.POINTER(MtTape)]),
+    "mt_shoot": (C.c_int, [_HANDLE, C.POINTER(MtShoot)]),
     "mt_observe": (C.c_int, [_HANDLE]),
     "mt_check_done": (C.c_int, [_HANDLE]),
     "mt_get": (C.c_int, [_HANDLE, C.c_int, C.c_void_p, C.c_int64, C.c_int]),

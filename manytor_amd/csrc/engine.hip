@@ -762,6 +762,43 @@ void launch_tape(mt_handle h, const StepArgs& a, const TapeArgs& r) {
   MT_DISPATCH_D(h->D, launch_tape_d, h, a, r);
 }
 
+// mt_shoot's commit: rollout_tape_kernel with every env following the plane its evaluation chose (SELECT).  One form, no
+// next-step prefetch (it was measured for the plain tape only).
+template <class Tbl>
+void launch_tape_select_t(mt_handle h, const StepArgs& a, const TapeArgs& r) {
+  const size_t lds = (size_t)3 * h->K * kBlock * sizeof(float);
+  if (lds > 65536)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_tape_kernel<Tbl, false, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((rollout_tape_kernel<Tbl, false, true>), grid_for(a.n), dim3(kBlock), lds, h->stream, a, r);
+}
+template <int D>
+void launch_tape_select_d(mt_handle h, const StepArgs& a, const TapeArgs& r) {
+  launch_tape_select_t<RtTable<D>>(h, a, r);
+}
+void launch_tape_select(mt_handle h, const StepArgs& a, const TapeArgs& r) {
+  if (h->static_kind == 1) return launch_tape_select_t<Ref4Table>(h, a, r);
+  if (h->static_kind == 2) return launch_tape_select_t<Dh7Table>(h, a, r);
+  MT_DISPATCH_D(h->D, launch_tape_select_d, h, a, r);
+}
+
+// shoot_kernel on the whole batch: a block per 64 envs, its four waves share the candidates (kernels.h).
+template <class Tbl>
+void launch_shoot_t(mt_handle h, const StepArgs& a, const ShootArgs& r) {
+  // targets [3K][64] + the four waves' (best return, index) pairs: 7.3 KB at K = 7, 26 KB at K = 32
+  const size_t lds = ((size_t)3 * h->K + 2 * kShootWaves) * kShootEnvs * sizeof(float);
+  hipLaunchKernelGGL((shoot_kernel<Tbl>), dim3((unsigned)((a.n + kShootEnvs - 1) / kShootEnvs)), dim3(kBlock), lds, h->stream, a, r);
+}
+template <int D>
+void launch_shoot_d(mt_handle h, const StepArgs& a, const ShootArgs& r) {
+  launch_shoot_t<RtTable<D>>(h, a, r);
+}
+void launch_shoot(mt_handle h, const StepArgs& a, const ShootArgs& r) {
+  if (h->static_kind == 1) return launch_shoot_t<Ref4Table>(h, a, r);
+  if (h->static_kind == 2) return launch_shoot_t<Dh7Table>(h, a, r);
+  MT_DISPATCH_D(h->D, launch_shoot_d, h, a, r);
+}
+
 // The rollout kernels implement the default trigonometry and the reference's frame rows only.
 bool fusable(mt_handle h) { return h->trig == 0 && !h->lds_table && !h->trace && !h->custom_frames; }
 
@@ -1141,6 +1178,8 @@ const char* mt_describe_dispatch(mt_handle h) {
       // mt_rollout_tape: one form for every batch size (the lane-split and two-chain forms do not exist for it)
       ",\"tape\":{\"usable\":" + b(fusable(h)) + ",\"lanes_per_env\":1,\"chains\":1,\"prefetch\":" + b(tape_prefetches(h)) +
       ",\"nt_loads\":" + b(h->tape_nt_loads) + "}" +
+      // mt_shoot: a block scores all candidates of 64 envs, one wave per candidate at a time
+      ",\"shoot\":{\"usable\":" + b(fusable(h)) + ",\"envs_per_block\":" + num(kShootEnvs) + ",\"waves_per_block\":" + num(kShootWaves) + "}" +
       ",\"reset\":{\"lanes_per_env\":" + num(h->reset_split ? 4 : 1) + "}" +
       ",\"overrides\":\"" + h->overrides + "\"" +
       ",\"policy\":{\"step_split4_max\":" + num(P.step_split4_max) + ",\"step_split2_max\":" + num(P.step_split2_max) +
@@ -1955,6 +1994,77 @@ int mt_rollout_tape(mt_handle h, const mt_tape* tape) {
     h->codes_valid = false;             // the kernel writes targets as floats only
   }
   return check_launch(h, "rollout_tape_kernel");
+}
+
+int mt_shoot(mt_handle h, const struct mt_shoot* s) {
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  MT_REQUIRE(h, s != nullptr, "shoot is NULL");
+  MT_REQUIRE(h, s->struct_size == (int32_t)sizeof(struct mt_shoot), "mt_shoot.struct_size does not match this library");
+  MT_REQUIRE(h, s->reserved == 0, "mt_shoot.reserved must be 0");
+  MT_REQUIRE(h, (s->flags & ~MT_SHOOT_AUTO_RESET) == 0, "mt_shoot.flags: unknown MT_SHOOT_* flag");
+  const bool auto_reset = (s->flags & MT_SHOOT_AUTO_RESET) != 0;
+  MT_REQUIRE(h, s->n_steps >= 0, "mt_shoot.n_steps must be >= 0");
+  MT_REQUIRE(h, s->n_candidates >= 1 && s->n_candidates <= 64, "mt_shoot.n_candidates must be 1..64");
+  MT_REQUIRE(h, s->commit_steps >= 0 && s->commit_steps <= s->n_steps, "mt_shoot.commit_steps must be 0..n_steps");
+  MT_REQUIRE(h, !(auto_reset && s->commit_steps == 0), "MT_SHOOT_AUTO_RESET with mt_shoot.commit_steps == 0: an evaluation re-arms nothing");
+  if (!fusable(h)) {  // the rollout kernels do not implement these
+    const char* what = h->custom_frames ? "custom obs_frame / ee_frame"
+                       : h->trace       ? "MT_FLAG_TRACE"
+                       : h->lds_table   ? "MT_FLAG_DH_IN_LDS"
+                       : h->trig == 2   ? "MT_FLAG_HW_TRIG"
+                       : (h->cfg.flags & MT_FLAG_DIRECT_TRIG) ? "MT_FLAG_DIRECT_TRIG"
+                       : h->trig == 1   ? "substeps beyond the recurrence's reach (per-pose trigonometry)"
+                                        : "a profiling flag (MT_FLAG_ABLATE_*)";
+    return fail(h, MT_ERR_UNSUPPORTED, std::string("mt_shoot: not available on a handle with ") + what);
+  }
+  if (!h->is_reset) return fail(h, MT_ERR_STATE, "mt_shoot before mt_reset / mt_reset_random");
+  if (s->n_steps == 0) return MT_OK;
+  const int H = s->commit_steps;
+  MT_REQUIRE(h, s->actions != nullptr, "mt_shoot.actions is NULL");
+  MT_REQUIRE(h, s->ld >= h->n, "mt_shoot.ld is smaller than n_envs");
+  MT_REQUIRE(h, s->cand_stride >= (int64_t)s->n_steps * h->D * s->ld, "mt_shoot.cand_stride is smaller than n_steps * dof * ld");
+  MT_REQUIRE(h, !s->returns_out || s->ret_ld >= h->n, "mt_shoot.ret_ld is smaller than n_envs");
+  MT_REQUIRE(h, !(H > 0 && s->best_out == nullptr), "mt_shoot.best_out is NULL with commit_steps > 0");
+  MT_REQUIRE(h, !(H > 0 && (s->reward_log || s->done_log)) || s->log_ld >= h->n, "mt_shoot.log_ld is smaller than n_envs");
+  MT_ENTER(h);
+  ShootArgs e{};
+  e.plans = s->actions;
+  e.ld = s->ld;
+  e.cand_stride = s->cand_stride;
+  e.returns_out = s->returns_out;
+  e.ret_ld = s->ret_ld;
+  e.best_out = s->best_out;
+  e.best_return_out = s->best_return_out;
+  e.T = s->n_steps;
+  e.C = s->n_candidates;
+  launch_shoot(h, h->args, e);  // reads the state, writes the caller's rows only
+  int rc = check_launch(h, "shoot_kernel");
+  if (rc || H == 0) return rc;
+  // the commit: what mt_rollout_tape(n_steps = H, the gathered tape) does, host bookkeeping included
+  if (auto_reset) {
+    h->args.seed_lo = (uint32_t)s->seed;
+    h->args.seed_hi = (uint32_t)(s->seed >> 32);
+    int rcg = order_behind_inplace_gather(h, h->stream);  // the in-kernel re-arm writes MT_F_LAST_RETURN
+    if (rcg) return rcg;
+  }
+  TapeArgs r{};
+  r.tape = s->actions;
+  r.tape_ld = s->ld;
+  r.reward_log = s->reward_log;
+  r.done_log = s->done_log;
+  r.log_ld = s->log_ld;
+  r.return_out = s->return_out;
+  r.T = H;
+  r.auto_reset = auto_reset ? 1u : 0u;
+  r.seed_lo = (uint32_t)s->seed;
+  r.seed_hi = (uint32_t)(s->seed >> 32);
+  r.radius = h->cfg.radius;
+  r.best = s->best_out;
+  r.cand_stride = s->cand_stride;
+  launch_tape_select(h, h->args, r);
+  h->args.flags &= ~kFlagWholeGoals;  // tape angles are anybody's floats
+  h->codes_valid = false;             // the kernel writes targets as floats only
+  return check_launch(h, "rollout_tape_kernel<SELECT>");
 }
 
 int mt_observe(mt_handle h) {

@@ -2175,6 +2175,9 @@ struct TapeArgs {
   uint32_t auto_reset, dry_run, nt_loads;
   uint32_t seed_lo, seed_hi;  // keys the targets of re-armed envs
   float radius;
+  // SELECT (mt_shoot's commit): env i reads the plane its evaluation chose, tape + best[i] * cand_stride
+  const int32_t* best;   // [n] or NULL
+  int64_t cand_stride;   // elements between planes
 };
 
 // a tape row element: read once, so optionally non-temporal (wave-uniform choice)
@@ -2183,8 +2186,14 @@ __device__ __forceinline__ float tape_load(const float* row, LaneOffset<R>& o, b
   global_ptr<const float> p = (global_ptr<const float>)(uniform_row(row) + lane_offset(o));
   return nt ? __builtin_nontemporal_load(p) : *p;
 }
+// ... of the plane a lane chose for itself (SELECT): the one address of the kernel that is 64-bit per lane -- a plane may
+// start anywhere in a (C, T, D, ld) block of any size.  These rows were read by the evaluation a launch earlier.
+__device__ __forceinline__ float tape_load_plane(const float* row, uint64_t byte_off) {
+  return *(global_ptr<const float>)(uniform_row(row) + byte_off);
+}
 
-template <class Tbl, bool PREFETCH = false>
+// SELECT: the tape is a stack of planes r.cand_stride apart and env i follows plane r.best[i] (shoot_kernel's choice).
+template <class Tbl, bool PREFETCH = false, bool SELECT = false>
 __global__ __launch_bounds__(kBlock) void rollout_tape_kernel(const StepArgs a, const TapeArgs r) {
   extern __shared__ __attribute__((aligned(16))) float tile[];  // [3K][kBlock]
   constexpr int D = Tbl::D;
@@ -2198,11 +2207,14 @@ __global__ __launch_bounds__(kBlock) void rollout_tape_kernel(const StepArgs a, 
   float* col = tile + threadIdx.x;
   const bool commit = r.dry_run == 0;  // (wave-uniform: a launch argument)
   const bool nt = r.nt_loads != 0;
+  uint64_t plane = 0;  // byte offset of this env's column in its plane, read once
+  if constexpr (SELECT) plane = (uint64_t)(uint32_t)ldr(r.best, o4) * (uint64_t)r.cand_stride * 4u + (uint64_t)i * 4u;
+  auto row_load = [&](const float* row) { return SELECT ? tape_load_plane(row, plane) : tape_load(row, o4, nt); };
 
   const uint32_t all_alive = (a.K >= 32) ? 0xFFFFFFFFu : ((1u << a.K) - 1u);
   float g[D], cur[D];
 #pragma unroll
-  for (int j = 0; j < D; ++j) cur[j] = tape_load(r.tape + (int64_t)j * r.tape_ld, o4, nt);
+  for (int j = 0; j < D; ++j) cur[j] = row_load(r.tape + (int64_t)j * r.tape_ld);
 #pragma unroll
   for (int j = 0; j < D; ++j) g[j] = ldr(a.goals + j * ld, o4);
   uint32_t am = ldr(a.alive, o4);
@@ -2221,7 +2233,7 @@ __global__ __launch_bounds__(kBlock) void rollout_tape_kernel(const StepArgs a, 
     for (int j = 0; j < D; ++j) raw[j] = cur[j];
     if (PREFETCH && !last) {
 #pragma unroll
-      for (int j = 0; j < D; ++j) cur[j] = tape_load(r.tape + ((int64_t)(s + 1) * D + j) * r.tape_ld, o4, nt);
+      for (int j = 0; j < D; ++j) cur[j] = row_load(r.tape + ((int64_t)(s + 1) * D + j) * r.tape_ld);
     }
     bool bad = false;
 #pragma unroll
@@ -2299,7 +2311,7 @@ __global__ __launch_bounds__(kBlock) void rollout_tape_kernel(const StepArgs a, 
     }
     if (!PREFETCH && !last) {
 #pragma unroll
-      for (int j = 0; j < D; ++j) cur[j] = tape_load(r.tape + ((int64_t)(s + 1) * D + j) * r.tape_ld, o4, nt);
+      for (int j = 0; j < D; ++j) cur[j] = row_load(r.tape + ((int64_t)(s + 1) * D + j) * r.tape_ld);
     }
   }
 
@@ -2312,6 +2324,127 @@ __global__ __launch_bounds__(kBlock) void rollout_tape_kernel(const StepArgs a, 
   if (ended) str(a.episodes, o4, episode);
   if (dirty)
     for (int k = 0; k < 3 * a.K; ++k) str(a.points + (int64_t)k * ld, o4, col[k * kBlock]);
+}
+
+// ---------------------------------------------------------------------------
+// mt_shoot's evaluation: C candidate tapes per env scored from the SAME resident state, the best one named.  For env i
+// and candidate c, returns[c][i] is what rollout_tape_kernel's dry run writes to return_out[i] for plane c, bit for bit;
+// best[i] is the smallest c whose return is maximal.  Nothing resident is written.
+//
+// One block owns kShootEnvs = 64 consecutive envs; its four waves split the candidates (wave w scores c = w, w + 4, ...,
+// one after the other), lane l is env 64 b + l in every wave.  A wave is thus 64 consecutive, 64-aligned envs of ONE
+// candidate with the tail lanes of the last wave inactive -- the very lanes that share a wave in the tape kernel.  That
+// is what bit identity needs: route_kinematics takes its wide form per wave (__any), so an env's z-minimum can depend on
+// its wave-mates; candidates side by side in a wave would break it.
+//   state   : start pose and alive mask are loaded once per lane and kept in registers; every candidate restarts from
+//             them with nothing known about the pose (pose_valid = false), as the dry run does.
+//   targets : one READ-ONLY [3K][64] LDS tile shared by the four waves (24 KB at K = 32).  The dry run's dead-target
+//             zeroing serves the observation of a committing call; no return depends on it, so there is no
+//             per-candidate copy.
+//   a step  : what the tape kernel's intermediate steps run -- unusable_angle screening (held pose, NOT counted),
+//             route_kinematics<Tbl, 0, true, false> with the PoseCache kept across the steps of one candidate, within_box
+//             on the alive targets, the reward rule.  MT_FLAG_TERMINATE_ON_GROUND changes `done` only, and without a
+//             re-arm `done` feeds nothing a return depends on: there is nothing to compute for it.
+//   select  : every wave keeps (best return, its lowest index) per lane over its own candidates, visited in ascending
+//             order; the four pairs meet in 2 KB of LDS and wave 0 writes best / best_return.  No atomics, no init
+//             pass, no dependence between blocks: the result is a function of (state, plans) alone.
+// Per env: the state is read once (4 D + 4 + 12 K bytes) where C dry runs read it C times, 4 D T C bytes of plans, and
+// 4 C bytes of scores only where returns_out is given.
+// ---------------------------------------------------------------------------
+constexpr int kShootEnvs = 64;
+constexpr int kShootWaves = kBlock / 64;
+struct ShootArgs {
+  const float* plans;     // candidate c, step t, joint j, env i = plans[c * cand_stride + (t * D + j) * ld + i]
+  int64_t ld, cand_stride;
+  float* returns_out;     // [C][ret_ld] or NULL
+  int64_t ret_ld;
+  int32_t* best_out;      // [n] or NULL
+  float* best_return_out; // [n] or NULL
+  int32_t T, C;
+};
+
+template <class Tbl>
+__global__ __launch_bounds__(kBlock) void shoot_kernel(const StepArgs a, const ShootArgs r) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];  // [3K][64] targets, [4][64] best returns, [4][64] best indices
+  constexpr int D = Tbl::D;
+  const Tbl t = TableMaker<Tbl>::make(a.dh);
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t i = blockIdx.x * kShootEnvs + lane;
+  const bool live = i < a.n;  // the tail lanes of the last block load, score and store nothing, but meet the barriers
+  LaneOffset<true> o4{i * 4u};
+  const int64_t ld = a.ld;
+  const float* col = tile + lane;
+  float* best_v = tile + 3 * a.K * kShootEnvs;
+  int32_t* best_c = reinterpret_cast<int32_t*>(best_v + kShootWaves * kShootEnvs);
+
+  float g0[D];
+  uint32_t am0 = 0u;
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) g0[j] = ldr(a.goals + j * ld, o4);
+    am0 = ldr(a.alive, o4);
+    for (int k = (int)w; k < 3 * a.K; k += kShootWaves) tile[k * kShootEnvs + lane] = ldr(a.points + (int64_t)k * ld, o4);
+  }
+  __syncthreads();
+
+  float top = -__builtin_inff();  // (a return is a finite sum of -1 / 0 / +1)
+  int32_t top_c = 0x7FFFFFFF;
+  if (live) {
+    for (int c = (int)w; c < r.C; c += kShootWaves) {  // (wave-uniform)
+      const float* plane = r.plans + (int64_t)c * r.cand_stride;
+      float g[D];
+#pragma unroll
+      for (int j = 0; j < D; ++j) g[j] = g0[j];
+      uint32_t am = am0;
+      float ret = 0.f;
+      PoseCache<D> pose;
+      bool pose_valid = false;
+      for (int s = 0; s < r.T; ++s) {
+        float act[D], raw[D], el[3], e[3];
+#pragma unroll
+        for (int j = 0; j < D; ++j) raw[j] = tape_load(plane + ((int64_t)s * D + j) * r.ld, o4, false);
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < D; ++j) bad |= unusable_angle(raw[j]);
+#pragma unroll
+        for (int j = 0; j < D; ++j) act[j] = bad ? g[j] : raw[j];  // the env holds its pose this step
+
+        const float zmin = route_kinematics<Tbl, 0, true, false>(t, a.S, a.inv_sm1, g, act, el, e, &pose, pose_valid, nullptr, false);
+        pose_valid = true;
+        const bool ground = zmin < 0.f;
+        uint32_t nam = am;
+        for (int k = 0; k < a.K; ++k) {
+          if (!((am >> k) & 1u)) continue;
+          const float* pk = col + 3 * k * kShootEnvs;
+          if (within_box(e, pk[0], pk[kShootEnvs], pk[2 * kShootEnvs], a.tol)) nam &= ~(1u << k);
+        }
+        ret += (float)(ground ? -1 : ((nam != am) ? 1 : 0));
+        am = nam;
+#pragma unroll
+        for (int j = 0; j < D; ++j) g[j] = act[j];
+      }
+      if (r.returns_out) str_stream(r.returns_out + (int64_t)c * r.ret_ld, o4, ret);
+      if (ret > top) {  // ascending c: a tie keeps the earlier candidate
+        top = ret;
+        top_c = c;
+      }
+    }
+  }
+  best_v[w * kShootEnvs + lane] = top;
+  best_c[w * kShootEnvs + lane] = top_c;
+  __syncthreads();
+  if (w != 0 || !live) return;
+#pragma unroll
+  for (int q = 1; q < kShootWaves; ++q) {  // a wave without candidates (C < 4) left (-inf, INT_MAX)
+    const float v = best_v[q * kShootEnvs + lane];
+    const int32_t vc = best_c[q * kShootEnvs + lane];
+    if (v > top || (v == top && vc < top_c)) {
+      top = v;
+      top_c = vc;
+    }
+  }
+  if (r.best_out) str(r.best_out, o4, top_c);
+  if (r.best_return_out) str_stream(r.best_return_out, o4, top);
 }
 
 // ---------------------------------------------------------------------------

@@ -348,14 +348,17 @@ class StepEngine:
                    1 if auto_reset else 0)
         self.version += 1
 
-    def _tape_tensor(self, actions, layout):
+    def _tape_tensor(self, actions, layout, candidates=False):
         """(tensor, ld) of a device action tape in the kernel's layout: f32, joint j of env i at step t at
         [(t * D + j) * ld + i].  A CUDA f32 (T, D, N) tensor with unit env stride and a uniform row pitch >= N goes in
-        zero-copy; anything else becomes a contiguous (T, D, N) f32 tensor on the engine's device."""
+        zero-copy; anything else becomes a contiguous (T, D, N) f32 tensor on the engine's device.
+        candidates=True: a stack of C such tapes, (C, T, D, N) or (C, T, N, D) -> (tensor, ld, cand_stride); read in place
+        under the same conditions when the candidate stride is uniform and the planes do not overlap."""
         import torch
         n, d = self.n_envs, self.dof
+        lead = "C, T" if candidates else "T"
         if layout not in ("env_major", "soa"):
-            raise ValueError("layout must be 'env_major' (T, N, D) or 'soa' (T, D, N)")
+            raise ValueError(f"layout must be 'env_major' ({lead}, N, D) or 'soa' ({lead}, D, N)")
         dev = torch.device("cuda", self.device)
         if _is_torch_tensor(actions):
             t = actions.detach()
@@ -365,18 +368,31 @@ class StepEngine:
                 a = a.astype(np.float64)
             a = np.ascontiguousarray(a)
             t = torch.from_numpy(a if a.flags.writeable else a.copy())
-        if t.dim() != 3 or tuple(t.shape[1:]) != ((d, n) if layout == "soa" else (n, d)):
-            want = f"(T, {d}, {n})" if layout == "soa" else f"(T, {n}, {d})"
-            raise ValueError(f"actions must be {want} for layout={layout!r}, got {tuple(t.shape)}")
-        if t.shape[0] == 0:
-            return torch.empty((0, d, n), dtype=torch.float32, device=dev), n
-        if (layout == "soa" and t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.stride(2) == 1
-                and t.stride(1) >= n and t.stride(0) == d * t.stride(1)):
-            return t, int(t.stride(1))
+        nd = 4 if candidates else 3
+        if t.dim() != nd or tuple(t.shape[-2:]) != ((d, n) if layout == "soa" else (n, d)):
+            want = f"({lead}, {d}, {n})" if layout == "soa" else f"({lead}, {n}, {d})"
+            what = "plans" if candidates else "actions"
+            raise ValueError(f"{what} must be {want} for layout={layout!r}, got {tuple(t.shape)}")
+        if not candidates:
+            if t.shape[0] == 0:
+                return torch.empty((0, d, n), dtype=torch.float32, device=dev), n
+            if (layout == "soa" and t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.stride(2) == 1
+                    and t.stride(1) >= n and t.stride(0) == d * t.stride(1)):
+                return t, int(t.stride(1))
+            t = t.to(device=dev, dtype=torch.float32)
+            if layout == "env_major":
+                t = t.permute(0, 2, 1)
+            return t.contiguous(), n
+        c, steps = int(t.shape[0]), int(t.shape[1])
+        if c == 0 or steps == 0:
+            return torch.empty((c, steps, d, n), dtype=torch.float32, device=dev), n, steps * d * n
+        if (layout == "soa" and t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.stride(3) == 1
+                and t.stride(2) >= n and t.stride(1) == d * t.stride(2) and t.stride(0) >= steps * t.stride(1)):
+            return t, int(t.stride(2)), int(t.stride(0))
         t = t.to(device=dev, dtype=torch.float32)
         if layout == "env_major":
-            t = t.permute(0, 2, 1)
-        return t.contiguous(), n
+            t = t.permute(0, 1, 3, 2)
+        return t.contiguous(), n, steps * d * n
 
     def rollout_actions(self, actions, *, layout="env_major", auto_reset=False, seed=0x5EED, log=False, returns=False,
                         dry_run=False):
@@ -422,6 +438,64 @@ class StepEngine:
         if not dry_run:
             self.version += 1
         return out or None
+
+    def shoot(self, plans, *, layout="soa", commit=0, auto_reset=False, seed=0x5EED, all_returns=False, log=False,
+              returns=False):
+        """A sampling planner's round in one call (mt_shoot): `plans` holds C candidate tapes of T steps per env, (C, T, D, N)
+        degrees (layout="soa"; a CUDA float32 tensor with unit env stride, a uniform row pitch >= N and a uniform candidate
+        stride is read in place) or (C, T, N, D) (layout="env_major", copied).  Every candidate is scored from the current
+        state exactly as rollout_actions(plans[c], dry_run=True, returns=True) scores it; `best` (N,) int32 names each env's
+        best one (the lowest index on a tie, numpy's argmax), `best_return` (N,) float32 its return.  commit=H > 0 then
+        executes steps 0..H-1 of each env's best plan for real, as rollout_actions(gathered[:H], auto_reset=, seed=) would.
+        all_returns=True adds `candidate_returns` (C, N); with a commit, log=True adds the committed steps' `reward` (H, N)
+        int8 and `done` (H, N) uint8 and returns=True their per-env sum `returns` (N,).  Device tensors in a dict.
+        Stream rules as rollout_actions; with commit == 0 nothing resident changes."""
+        import torch
+        commit = int(commit)
+        if auto_reset and commit == 0:
+            raise ValueError("auto_reset needs commit > 0: an evaluation re-arms nothing")
+        tape, ld, cand_stride = self._tape_tensor(plans, layout, candidates=True)
+        c, T, n = int(tape.shape[0]), int(tape.shape[1]), self.n_envs
+        if not 1 <= c <= 64:
+            raise ValueError(f"plans must hold 1..64 candidates, got {c}")
+        if not 0 <= commit <= T:
+            raise ValueError(f"commit must be 0..T = {T}, got {commit}")
+        dev = tape.device
+        alloc = torch.empty if T else torch.zeros                # (T == 0: the call is a no-op and writes nothing)
+        out = {"best": alloc(n, dtype=torch.int32, device=dev), "best_return": alloc(n, dtype=torch.float32, device=dev)}
+        if all_returns:
+            out["candidate_returns"] = alloc((c, n), dtype=torch.float32, device=dev)
+        if log:
+            out["reward"] = torch.empty((commit, n), dtype=torch.int8, device=dev)
+            out["done"] = torch.empty((commit, n), dtype=torch.uint8, device=dev)
+        if returns:
+            out["returns"] = (alloc if commit else torch.zeros)(n, dtype=torch.float32, device=dev)
+        arg = L.MtShoot()
+        arg.struct_size = C.sizeof(L.MtShoot)
+        arg.n_steps, arg.n_candidates, arg.commit_steps = T, c, commit
+        arg.actions = tape.data_ptr() if T else None
+        arg.ld, arg.cand_stride = ld, cand_stride
+        arg.returns_out = out["candidate_returns"].data_ptr() if all_returns else None
+        arg.ret_ld = n
+        arg.best_out = out["best"].data_ptr()
+        arg.best_return_out = out["best_return"].data_ptr()
+        arg.reward_log = out["reward"].data_ptr() if log and commit else None
+        arg.done_log = out["done"].data_ptr() if log and commit else None
+        arg.log_ld = n
+        arg.return_out = out["returns"].data_ptr() if returns and commit else None
+        arg.seed = int(seed)
+        arg.flags = L.SHOOT_AUTO_RESET if auto_reset else 0
+        arg.reserved = 0
+        cur = int(torch.cuda.current_stream(self.device).cuda_stream)
+        ordered = getattr(self, "_caller_stream", None) == cur   # the engine launches on torch's current stream
+        if not ordered:
+            torch.cuda.current_stream(self.device).synchronize()
+        self._call(self._lib.mt_shoot, C.byref(arg))
+        if not ordered:
+            self.sync()     # the plans and the outputs are torch's memory: done with before torch may reuse or read it
+        if commit and T:
+            self.version += 1
+        return out
 
     def observe(self):
         """Environment.get_observations (manytor.py:141-153); result in field OBS."""
