@@ -337,6 +337,13 @@ static void choose_dispatch(mt_handle h) {
     seen("MT_TAPE_NT");
   }
 
+  // ---- the ground test's interior poses on dense lanes of the block (kernels.h, GroundQueue); 0: the per-lane loop ----
+  h->ground_compact = true;
+  if (env_int("MT_GROUND_COMPACT", &v)) {
+    h->ground_compact = v != 0;
+    seen("MT_GROUND_COMPACT");
+  }
+
   if (h->custom_frames) h->lds_table = false;
   // The schedule of launches over `envs` envs, against the thresholds of their scope
   auto schedule_for = [&](int64_t envs, int64_t split4_max, int64_t split2_max, int64_t prefetch_other_max) {
@@ -379,10 +386,11 @@ struct StepVariant {
   bool flat = false;   // FLAT
   bool fresh = false;  // FRESH
   bool codes = false;  // CODES
+  bool gc = false;     // GC: the interior poses of the ground test on dense lanes of the block (kernels.h, GroundQueue)
 };
 constexpr unsigned variant_key(const StepVariant& v) {
   return (unsigned)v.trig | (unsigned)v.lds << 3 | (unsigned)v.lanes << 4 | (unsigned)(v.pf != 0) << 7 | (unsigned)v.tt << 8 |
-         (unsigned)v.flat << 9 | (unsigned)v.fresh << 10 | (unsigned)v.codes << 11;
+         (unsigned)v.flat << 9 | (unsigned)v.fresh << 10 | (unsigned)v.codes << 11 | (unsigned)v.gc << 12;
 }
 
 // Every instantiation the library holds, per table type.  A row without TT exists for sampled and for staged actions
@@ -394,6 +402,7 @@ constexpr StepVariant kRuntimeVariants[] = {  // RtTable<D>
     {.lds = true},
     {.lanes = 2}, {.lanes = 4},
     {.pf = kPrefetch}, {.pf = kPrefetch, .flat = true},
+    {.gc = true}, {.pf = kPrefetch, .gc = true}, {.pf = kPrefetch, .flat = true, .gc = true},
 };
 constexpr StepVariant kFramesVariants[] = {{.trig = 0}, {.trig = 1}};  // RtTableF<D>
 constexpr StepVariant kStaticVariants[] = {  // Ref4Table, Dh7Table
@@ -405,6 +414,9 @@ constexpr StepVariant kStaticVariants[] = {  // Ref4Table, Dh7Table
     {.pf = kPrefetch, .tt = true, .codes = true}, {.pf = kPrefetch, .tt = true, .flat = true, .codes = true},
     {.pf = 0, .tt = true, .fresh = true}, {.pf = kPrefetch, .tt = true, .fresh = true},
     {.pf = kPrefetch, .tt = true, .flat = true, .fresh = true},
+    {.gc = true}, {.pf = kPrefetch, .gc = true}, {.pf = kPrefetch, .flat = true, .gc = true},
+    {.pf = 0, .tt = true, .gc = true}, {.pf = kPrefetch, .tt = true, .gc = true}, {.pf = kPrefetch, .tt = true, .flat = true, .gc = true},
+    {.pf = kPrefetch, .tt = true, .codes = true, .gc = true}, {.pf = kPrefetch, .tt = true, .flat = true, .codes = true, .gc = true},
 };
 #pragma clang diagnostic pop
 
@@ -419,6 +431,25 @@ struct StepPlan {
   dim3 grid;
   bool exists = true;  // false: no such kernel for this handle's schedule (FRESH only)
 };
+
+// The block-cooperative ground test (kernels.h, GroundQueue; MT_GROUND_COMPACT) of the one-env-per-lane recurrence kernels
+// of a compile-time or runtime table.  Not on the single-env view (threads past the env would read outside its rows), not
+// with MT_FLAG_DEBUG_ZMIN (MT_F_ZMIN wants every pose of every env: the per-lane loop), not for the long arms (D >= 6: the
+// sequential schedule exists to fit 64 VGPRs, and both ends' state alive at the queue does not -- the runtime-table
+// kernels spill, the prefetch kernels go from 62 to 74 VGPRs; profiles/ground_compaction_kernel_resources.md).
+static bool ground_compacts(const mt_engine* h, bool whole_rows) {
+  return h->ground_compact && whole_rows && h->trig == 0 && !h->lds_table && !h->custom_frames &&
+         !(h->cfg.flags & MT_FLAG_DEBUG_ZMIN) && h->D <= 5;
+}
+template <int D>
+static void ground_queue_bytes_d(size_t* out) { *out = sizeof(GroundQueue<RtTable<D>>); }
+static size_t ground_queue_bytes(const mt_engine* h) {  // the static LDS the GC kernels of this handle's table add
+  if (h->static_kind == 1) return sizeof(GroundQueue<Ref4Table>);
+  if (h->static_kind == 2) return sizeof(GroundQueue<Dh7Table>);
+  size_t bytes = 0;
+  MT_DISPATCH_D(h->D, ground_queue_bytes_d, &bytes);
+  return bytes;
+}
 
 // THE rules of which step kernel a launch of `n` envs gets -- every variant gives the same bits, so this is about time only:
 //   scope  whose schedule: the whole batch, one chain's 256-aligned range of it, or the single-env view (batch schedule).
@@ -475,9 +506,10 @@ StepPlan plan_step(const mt_engine* h, mt_engine::Scope scope, int64_t n, bool s
   v.flat = v.pf && n >= h->flat_from;   // HBM-bound launches: kernels.h, LaneOffset<false>
   // the prefetch kernels read the targets as their codes while those are valid (kernels.h, CODES: 28 B per env less)
   v.codes = v.pf && v.tt && codes;
+  v.gc = ground_compacts(h, whole_rows);
   if (v.pf && v.tt) {  // see step_blocks_per_cu
     p.blocks_per_cu = step_blocks_per_cu(h, n);
-    p.lds_bytes = lds_pad_for_blocks(p.blocks_per_cu, kTrigEntries * sizeof(SinCos));
+    p.lds_bytes = lds_pad_for_blocks(p.blocks_per_cu, kTrigEntries * sizeof(SinCos) + (v.gc ? ground_queue_bytes(h) : 0));
   }
   return p;
 }
@@ -489,14 +521,16 @@ void launch_variant(const StepPlan& p, hipStream_t stream, const StepArgs& args)
   if constexpr (V.lanes > 1)
     hipLaunchKernelGGL((step_split_kernel<Tbl, SAMPLE, V.lanes, V.tt>), p.grid, dim3(kBlock), p.lds_bytes, stream, args);
   else
-    hipLaunchKernelGGL((step_kernel<Tbl, SAMPLE, V.trig, V.lds, V.pf, V.tt, V.flat, V.fresh, V.codes>), p.grid, dim3(kBlock),
+    hipLaunchKernelGGL((step_kernel<Tbl, SAMPLE, V.trig, V.lds, V.pf, V.tt, V.flat, V.fresh, V.codes, V.gc>), p.grid, dim3(kBlock),
                        p.lds_bytes, stream, args);
 }
 // ... if row I is the plan's variant (false: it is not)
 template <class Tbl, const auto& ROWS, size_t I>
 bool launch_row(const StepPlan& p, hipStream_t stream, const StepArgs& args) {
   if (variant_key(p.v) != variant_key(ROWS[I])) return false;
-  if (p.sample)
+  if constexpr (ROWS[I].gc && Tbl::D >= 6)
+    return false;  // never planned (ground_compacts), not instantiated
+  else if (p.sample)
     launch_variant<Tbl, true, ROWS, I>(p, stream, args);
   else if constexpr (!ROWS[I].tt)
     launch_variant<Tbl, false, ROWS, I>(p, stream, args);
@@ -521,6 +555,12 @@ void launch_plan_d(const StepPlan& p, hipStream_t stream, const StepArgs& args, 
 // Launches the kernel a plan names.  A plan outside the tables above is a bug in plan_step, not a condition to run past.
 void launch_plan(const StepPlan& p, hipStream_t stream, const StepArgs& args) {
   bool launched = false;
+  // GC kernels keep the threads past the end of the batch up to the barriers, and those load at their own offsets: the rows
+  // must cover the grid (whole-row launches do: ld >= the batch rounded up to blocks; ground_compacts keeps the rest out)
+  if (p.v.gc && (int64_t)p.grid.x * kBlock > args.ld) {
+    std::fprintf(stderr, "manytor: a ground-compacting step launch of %u blocks over rows of %lld\n", p.grid.x, (long long)args.ld);
+    std::abort();
+  }
   if (p.table == TableKind::kRef4)
     launched = launch_table<Ref4Table, kStaticVariants>(p, stream, args);
   else if (p.table == TableKind::kDh7)
@@ -1181,6 +1221,9 @@ const char* mt_describe_dispatch(mt_handle h) {
       // mt_shoot: a block scores all candidates of 64 envs, one wave per candidate at a time
       ",\"shoot\":{\"usable\":" + b(fusable(h)) + ",\"envs_per_block\":" + num(kShootEnvs) + ",\"waves_per_block\":" + num(kShootWaves) + "}" +
       ",\"reset\":{\"lanes_per_env\":" + num(h->reset_split ? 4 : 1) + "}" +
+      // the ground test's interior poses on dense lanes of the block: the step launches that take it (the single-env view,
+      // the rollout, tape and shoot kernels never do)
+      ",\"ground_compact\":{\"enabled\":" + b(h->ground_compact) + ",\"step\":" + b(sb.v.gc) + ",\"chains\":" + b(sc.v.gc) + "}" +
       ",\"overrides\":\"" + h->overrides + "\"" +
       ",\"policy\":{\"step_split4_max\":" + num(P.step_split4_max) + ",\"step_split2_max\":" + num(P.step_split2_max) +
       ",\"prefetch_other_max\":" + num(P.prefetch_other_max) + ",\"fused_split4_max\":" + num(P.fused_split4_max) +

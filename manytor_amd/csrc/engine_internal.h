@@ -119,6 +119,7 @@ struct mt_engine {
   bool snap_valid = false;      // ... it did, and nothing has touched the returns since: mt_gather_returns_begin skips its copy
   bool tape_prefetch = false;   // mt_rollout_tape: the tape row of step s + 1 requested before the kinematics of step s (MT_TAPE_PREFETCH)
   bool tape_nt_loads = false;   // ... and the tape read with non-temporal loads (MT_TAPE_NT)
+  bool ground_compact = true;   // step_kernel<.., GC>: the ground test's interior poses on dense lanes of the block (MT_GROUND_COMPACT)
   std::string overrides;        // the MT_* overrides choose_dispatch saw ("NAME=value,...")
   std::string describe;         // mt_describe_dispatch's text
   hipStream_t chain_streams[kMaxChains] = {nullptr, nullptr, nullptr, nullptr};  // [0] unused: chain 0 runs on `stream`

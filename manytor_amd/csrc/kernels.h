@@ -16,6 +16,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "mt_math.h"
 #include "philox.h"
 #include "step_args.h"
@@ -857,6 +859,163 @@ __device__ __forceinline__ float route_kinematics(const Tbl& t, int S, float inv
   return route_kinematics_narrow<Tbl, TRIG, CACHED, TABLE>(t, S, inv_sm1, g, act, el, e, cache, cache_valid, trig, prev_whole);
 }
 
+// ---------------------------------------------------------------------------
+// The ground test of a block, with the interior poses run on dense lanes (step_kernel<.., GC>).
+//
+// The interior poses of a route yield one bit, zmin < 0, and both END poses are evaluated anyway (the action's for the
+// elbow and the end effector, the previous one because manytor.py:182-192 evaluates it again).  Where an end pose already
+// has a frame below ground the bit is decided and the S - 2 interior poses cannot change any output: 78 % of the env-steps
+// of a random rollout of the reference arm.  The undecided envs are spread evenly over the lanes (14 of a wave's 64 on
+// average), so no wave can skip the loop by itself; a block can: its undecided lanes park what the recurrence needs --
+// per joint 1 .. JN-1 the start (s, c), the end (s, c) and the increment (sd, cd) -- in an LDS queue, and after a barrier
+// the queued routes are dealt out as HALF routes (the forward half from the previous pose, the backward half from the
+// action: independent chains, the unit route_kinematics_split_narrow walks) to the first 2 Q lanes of the block, rotated by
+// blockIdx.x so that the working waves of the blocks resident on a CU fall on different SIMDs.  A working lane runs
+// rotate_pose / chain_z on the owner's values in the owner's order and leaves the half's minimum in LDS; after a second
+// barrier the owner combines the two halves with its end poses.  The same arithmetic on the same inputs in another lane
+// (-(s * -sd) == s * sd exactly, min is order-free), so zmin < 0 is the same bit for every env.
+//
+// The queue holds kCap routes.  An undecided lane that finds it full (the first step of an episode leaves 47 % undecided,
+// staged actions can leave a whole block) walks its own two halves in place, like route_kinematics_narrow: any number of
+// undecided envs, 0 .. 256, is handled without rounds.  Waves with a wide route (route_kinematics_wide) evaluate all
+// poses themselves, queue nothing, and lend their lanes to the block's queue like every other wave.
+// Every thread of the block must reach both barriers: lanes past the end of the batch come along as decided lanes.
+// ---------------------------------------------------------------------------
+template <class Tbl>
+struct GroundQueue {
+  static constexpr int kJoints = ZJoints<Tbl>::value - 1;  // the joints chain_z reads
+  static constexpr int kFields = 6 * kJoints;              // start (s, c), end (s, c), increment (sd, cd) per joint
+  // routes per block: at most kBlock / 2 (one half route per lane), fewer for long arms (<= 14 KB of LDS, whole waves)
+  static constexpr int kCap = (14336 / (4 * kFields) >= kBlock / 2) ? kBlock / 2 : (14336 / (4 * kFields)) / 32 * 32;
+  static_assert(kCap >= 32 && 2 * kCap <= kBlock, "one half route per lane");
+  uint32_t count;             // undecided lanes of the block so far (may exceed kCap: the rest walk their own routes)
+  float zres[2 * kCap];       // [2 r + half] minimum z over the interior poses of that half of route r
+  float field[kFields][kCap]; // field-major: the lanes of a wave write / read consecutive words
+};
+
+// min z over this half's interior poses: `n_half` rotations from (s, c) by (sd, cd), of which the first `mine` count (the
+// halves differ by at most one pose; the loop bound stays uniform).  3e38 when the half has no pose.
+template <class Tbl>
+__device__ __forceinline__ float half_route_zmin(const Tbl& t, float (&s)[Tbl::D], float (&c)[Tbl::D], const float (&sd)[Tbl::D],
+                                                 const float (&cd)[Tbl::D], int n_half, int mine) {
+  constexpr int D = Tbl::D;
+  constexpr int JN = ZJoints<Tbl>::value;
+  float zm = 3.0e38f, zo, ze;
+#pragma unroll 2
+  for (int it = 1; it <= n_half; ++it) {
+    rotate_pose<D, JN, +1>(s, c, sd, cd);
+    chain_z<Tbl>(s, c, t, zo, ze);
+    if (it <= mine) zm = fminf(zm, fminf(zo, ze));
+  }
+  return zm;
+}
+
+struct NoGroundQueue {  // what a kernel without the queue declares in its place: never referenced, no LDS
+  uint32_t count;
+};
+__device__ __forceinline__ void ground_queue_reset(uint32_t* count) {  // ahead of a barrier that every thread reaches
+  if (threadIdx.x == 0) *count = 0u;
+}
+
+// route_kinematics for the recurrence (TRIG == 0) of a whole block; `live` = this lane has an env.  Called by every
+// thread of the block, after a barrier behind ground_queue_reset.
+template <class Tbl, bool TABLE>
+__device__ __forceinline__ float route_kinematics_block(const Tbl& t, int S, float inv_sm1, const float (&g)[Tbl::D],
+                                                        const float (&act)[Tbl::D], float (&el)[3], float (&e)[3],
+                                                        const SinCos* trig, bool prev_whole, bool live, GroundQueue<Tbl>& q) {
+  constexpr int D = Tbl::D;
+  constexpr int JN = ZJoints<Tbl>::value;
+  constexpr int kCap = GroundQueue<Tbl>::kCap;
+  const int nf = (S - 1) / 2;   // forward poses k = 1..nf
+  const int nb = S - 2 - nf;    // backward poses k = S-2..nf+1   (nb = nf or nf-1)
+  float zmin;
+  bool undecided = false;
+  float sF[D], cF[D], sA[D], cA[D], sd[D], cd[D];
+  if (__builtin_expect(__any(live && wide_route<Tbl, TABLE>(g, act, prev_whole)), 0)) {
+    zmin = route_kinematics_wide<Tbl, false>(t, S, g, act, el, e, nullptr);
+  } else {
+    // the two end poses, as route_kinematics_narrow evaluates them
+    float st[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) st[j] = (act[j] - g[j]) * inv_sm1;
+    float p[D][3], zo, ze;
+    action_sincos<Tbl, TABLE>(t, act, sA, cA, trig);
+    chain_all<Tbl>(sA, cA, t, p);
+    pick_frames<Tbl>(t, p, el, e);
+    zmin = fminf(el[2], e[2]);
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      sF[j] = 0.f;
+      cF[j] = 1.f;
+    }
+    prev_pose_sincos<Tbl, TABLE>(t, g, sF, cF, trig, prev_whole);
+    chain_z<Tbl>(sF, cF, t, zo, ze);
+    zmin = fminf(zmin, fminf(zo, ze));
+    sincos_increment<D, JN>(st, sd, cd);
+    sA[0] = 0.f;
+    cA[0] = 1.f;
+    undecided = live && !(zmin < 0.f);
+  }
+
+  // a place in the block's queue for every undecided lane: one LDS atomic per wave
+  const unsigned long long um = __ballot(undecided);
+  uint32_t slot = kCap;
+  if (um != 0ull) {
+    uint32_t base = 0u;
+    if ((threadIdx.x & 63u) == 0u) base = atomicAdd(&q.count, (uint32_t)__popcll(um));
+    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+    slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(um >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)um, 0u));
+  }
+  const bool queued = undecided && slot < (uint32_t)kCap;
+  if (queued) {
+#pragma unroll
+    for (int j = 1; j < JN; ++j) {
+      float(*f)[kCap] = q.field + 6 * (j - 1);
+      f[0][slot] = sF[j];
+      f[1][slot] = cF[j];
+      f[2][slot] = sA[j];
+      f[3][slot] = cA[j];
+      f[4][slot] = sd[j];
+      f[5][slot] = cd[j];
+    }
+  }
+  if (undecided && !queued) {  // the queue was full: this lane's own two halves (ahead of the barrier: nothing of it stays live across the queue's work)
+    zmin = fminf(zmin, half_route_zmin<Tbl>(t, sF, cF, sd, cd, nf, nf));
+#pragma unroll
+    for (int j = 1; j < JN; ++j) sd[j] = -sd[j];
+    zmin = fminf(zmin, half_route_zmin<Tbl>(t, sA, cA, sd, cd, nf, nb));
+  }
+  __syncthreads();  // the queue is complete
+
+  const uint32_t routes = q.count < (uint32_t)kCap ? q.count : (uint32_t)kCap;
+  const uint32_t w = (threadIdx.x + 64u * (blockIdx.x & 3u)) & (uint32_t)(kBlock - 1);  // this lane's half route
+  if (w < 2u * routes) {
+    const uint32_t r = w >> 1;
+    const bool backward = (w & 1u) != 0u;
+    float sW[D], cW[D], sdW[D], cdW[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      sW[j] = 0.f;
+      cW[j] = 1.f;
+      sdW[j] = 0.f;
+      cdW[j] = 1.f;
+    }
+#pragma unroll
+    for (int j = 1; j < JN; ++j) {
+      const float(*f)[kCap] = q.field + 6 * (j - 1);
+      sW[j] = backward ? f[2][r] : f[0][r];
+      cW[j] = backward ? f[3][r] : f[1][r];
+      const float sdj = f[4][r];
+      sdW[j] = backward ? -sdj : sdj;  // rotate by -delta: the sign rides in the operand
+      cdW[j] = f[5][r];
+    }
+    q.zres[w] = half_route_zmin<Tbl>(t, sW, cW, sdW, cdW, nf, backward ? nb : nf);
+  }
+  __syncthreads();  // the halves' minima are in place
+  if (queued) zmin = fminf(zmin, fminf(q.zres[2u * slot], q.zres[2u * slot + 1u]));
+  return zmin;
+}
+
 // An env finished its episode `episode` with return `ret` and is being re-armed: keep the return in the ring
 // (slot = number of episodes it finished before, modulo the ring size) and in the one-slot last_return row.
 __device__ __forceinline__ void record_finished(const StepArgs& a, uint32_t i, uint32_t episode, float ret) {
@@ -924,9 +1083,10 @@ __device__ __forceinline__ void draw_targets_wave(uint64_t seed, uint64_t env0, 
 //            their floats: 56 instead of 84 B per env at K = 7, of the 233 a step moves.  Only while the host knows the codes
 //            to match MT_F_POINTS (engine_internal.h: codes_valid); a dead target's code is zeroed with its floats.
 template <class Tbl, bool SAMPLE, int TRIG, bool LDS, int PF = 0, bool TT = false, bool FLAT = false, bool FRESH = false,
-          bool CODES = false>
+          bool CODES = false, bool GC = false>
 __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) void step_kernel(const StepArgs a) {
   constexpr int D = Tbl::D;
+  static_assert(!GC || (TRIG == 0 && !LDS && !FRESH), "the block-cooperative ground test serves the recurrence");
   static_assert(!TT || (SAMPLE && TRIG == 0 && !LDS && ActionTrigTable<Tbl>::value), "the table serves sampled actions of a static table");
   static_assert(!FRESH || TT, "the reset prologue exists for the sampled-action kernels of the static tables");
   static_assert(!CODES || (PF && TT && !FRESH), "codes are read by the prefetch kernels of the static tables");
@@ -934,8 +1094,13 @@ __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) voi
   __shared__ uint8_t fresh_slots[FRESH ? kBlock / 64 : 1][64];    // FRESH: draw_targets_wave's scratch
   __shared__ DhConst sh;
   __shared__ __attribute__((aligned(16))) SinCos trig_lds[TT ? kTrigEntries : 1];
+  __shared__ std::conditional_t<GC, GroundQueue<Tbl>, NoGroundQueue> ground_q;  // (the queue's type exists for GC kernels only)
   float4 trig_v;
   if (TT) trig_v = trig_table_load(a.trig_table);
+  if constexpr (GC) {
+    ground_queue_reset(&ground_q.count);
+    if (!TT) __syncthreads();  // (TT: the barrier of trig_table_commit below)
+  }
   if (LDS) {
     const float* src = reinterpret_cast<const float*>(&a.dh);
     float* dst = reinterpret_cast<float*>(&sh);
@@ -946,7 +1111,10 @@ __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) voi
 
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;  // 32-bit lane offset: rows are addressed as uniform base + i
   LaneOffset<!FLAT> o4{i * 4u}, o1{i};  // byte offsets of this lane in the 32-bit rows / the byte rows
-  if (!TT && i >= a.n) return;  // (TT, and with it FRESH: every thread stays up to the barrier / takes part in the draw)
+  // (TT, and with it FRESH: every thread stays up to the barrier / takes part in the draw; GC: up to the ground test's
+  // barriers, as a lane without an env -- its loads stay inside the rows, it stores nothing)
+  const bool live = i < a.n;
+  if (!TT && !GC && !live) return;
   const int64_t ld = a.ld;
   // Read ahead of every row access: behind one (its lane offset renewal is an opaque asm to the memory analysis) the
   // word is no longer provably unclobbered, and the s_load turns into a vector load with an s_waitcnt vmcnt(0) behind
@@ -1031,7 +1199,14 @@ __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) voi
     if (bad) {  // the env holds its pose this step; the call is counted (mt_bad_action_count)
 #pragma unroll
       for (int j = 0; j < D; ++j) act[j] = g[j];
-      atomicAdd(a.bad_actions, 1u);
+      if (!GC || live) atomicAdd(a.bad_actions, 1u);
+    }
+  }
+  if constexpr (GC) {  // a lane without an env: whatever the rows hold past the batch stays out of the arithmetic
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      g[j] = live ? g[j] : 0.f;
+      if (!SAMPLE) act[j] = live ? act[j] : 0.f;
     }
   }
   MT_STAMP(a, i, 1);  // action known (Philox done / staged action loaded)
@@ -1039,16 +1214,23 @@ __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) voi
     // (complete_before_here(act) -- the Philox block ahead of this wait -- was measured here: nothing at >= 262 144 envs,
     // +1 % at 131 072; the lane-split kernels gain 1-2 % and have it: profiles/r03_ab_philox_before_wait.txt)
     trig_table_commit(trig_lds, trig_v);  // the table load has had the pose loads to arrive
-    if (i >= a.n) return;
+    if (!GC && !live) return;
   }
-  if (kLean) {  // goals = action (manytor.py:184): the old pose is in registers already
+  if (kLean && (!GC || live)) {  // goals = action (manytor.py:184): the old pose is in registers already
 #pragma unroll
     for (int j = 0; j < D; ++j) str(a.goals + j * ld, o4, act[j]);
   }
 
   float el[3], e[3];
-  const float zmin = route_kinematics<Tbl, TRIG, false, TT>(t, a.S, a.inv_sm1, g, act, el, e, nullptr, false, trig_lds,
-                                                            (a.flags & kFlagWholeGoals) != 0);
+  float zmin;
+  if constexpr (GC) {
+    zmin = route_kinematics_block<Tbl, TT>(t, a.S, a.inv_sm1, g, act, el, e, trig_lds, (a.flags & kFlagWholeGoals) != 0, live,
+                                           ground_q);
+    if (!live) return;  // behind the last barrier
+  } else {
+    zmin = route_kinematics<Tbl, TRIG, false, TT>(t, a.S, a.inv_sm1, g, act, el, e, nullptr, false, trig_lds,
+                                                  (a.flags & kFlagWholeGoals) != 0);
+  }
   const bool ground = zmin < 0.f;  // manytor.py:191
   if (a.zmin) str_stream(a.zmin, o4, zmin);  // MT_FLAG_DEBUG_ZMIN: wave-uniform branch on an SGPR pointer, NULL by default
   if (kLean && !PF && !FRESH) {
