@@ -40,7 +40,7 @@ extern "C" {
 #define MT_API
 #endif
 
-#define MT_VERSION 410          /* major*10000 + minor*100 + patch */
+#define MT_VERSION 420          /* major*10000 + minor*100 + patch */
 #define MT_MAX_DOF 8
 #define MT_MAX_TARGETS 32
 #define MT_MAX_RETURN_RING 64
@@ -304,6 +304,65 @@ struct mt_shoot {          /* the struct and the call share the name, so the typ
   uint32_t flags, reserved;
 };
 MT_API int mt_shoot(mt_handle h, const struct mt_shoot* s);
+
+/* One iteration of the cross-entropy method (CEM) in one call: draw C candidate plans per env around (mean, sigma), score
+ * them as mt_shoot does, pick the best and the E best ("elites"), refit (mean, sigma) from the elites and (commit_steps =
+ * H > 0) execute the first H steps of the best plan.  No (C, T, D, N) block exists: the candidates are drawn in the kernel.
+ *
+ * The candidate stream.  For the global env id e = env_id_base + i, candidate c, step t and joint j:
+ *   w = Philox-4x32-10 block of counter (e_lo, e_hi[23:0] | 3 << 24, draw, (c << 24) | (b << 16) | t), key = seed,
+ *       b = 0 and word j for j < 4, b = 1 and word j - 4 for j >= 4
+ *   z = (float)((int)(sum of the four bytes of w) - 510) * KZ,  KZ = the fp32 nearest to 1 / sqrt(21845)
+ *       (Irwin-Hall of four uniform bytes: mean 0, variance 1, |z| <= 3.4506; the multiply is the only rounding)
+ *   x = mean[(t*D + j)*ld + i] + sigma[(t*D + j)*ld + i] * z      (an fp32 multiply, then an fp32 add)
+ *   x is handed on as it is when it is unusable (NaN, +-inf, beyond +-32768 degrees: the step holds the pose, as for any
+ *   tape), else clamped: min(max(x, lo), hi).  MT_CEM_KEEP_MEAN: candidate 0 has z = 0, i.e. it is the clamped mean.
+ * mean and sigma are device memory and cannot be screened: a non-finite mean or sigma of env i makes env i's candidates
+ * score as held poses and leaves its refit unspecified; no other env's outputs change.
+ *
+ * mt_sample_plans writes exactly this block P, P[c][t][j][i] = plans_out[c*cand_stride + (t*D + j)*ld + i] (mt_shoot's
+ * layout; plans_out is DEVICE f32).  It reads n_steps, n_candidates, draw, mean, sigma, ld, lo, hi, seed and flags only,
+ * and needs no reset.
+ *
+ * mt_cem, with P the block mt_sample_plans writes for the same struct:
+ *   evaluation  returns_out, best_out, best_return_out are, bit for bit, what mt_shoot writes for actions = P (the lowest
+ *               index wins a tie; nothing resident changes; a refused angle is not counted).
+ *   elites      order the candidates of env i by (return descending, index ascending); the first E are its elites and
+ *               elite_mask_out[i] has exactly their bits set.
+ *   refit       in fp32, one rounding per operation: with the elites e0 < e1 < ... and x_k = P[e_k][t][j][i],
+ *               m = (((x_0 + x_1) + x_2) + ...) * invE, invE = the fp32 nearest to 1 / E;  d_k = x_k - m;
+ *               v = (((d_0*d_0 + d_1*d_1) + ...)) * invE;  mean_out = m, sigma_out = max(sqrt(v), sigma_min).
+ *               mean_out / sigma_out may be EXACTLY mean / sigma (same pointer, out_ld == ld): the refit is then in place.
+ *               Any other overlap of mean_out / sigma_out / chosen_out with mean / sigma or each other is refused.
+ *   commit      chosen_out[(t*D + j)*chosen_ld + i] = P[best[i]][t][j][i] for t < H, and the handle is afterwards where
+ *               mt_rollout_tape(n_steps = H, actions = chosen_out, the same seed, MT_TAPE_AUTO_RESET iff MT_CEM_AUTO_RESET)
+ *               leaves it: every field, the logs, return_out, mt_bad_action_count.
+ * At most two launches on the handle's stream, no allocation, no host wait: legal under stream capture.
+ * MT_ERR_UNSUPPORTED / MT_ERR_STATE as mt_shoot; n_steps == 0 is a no-op; lo, hi (finite, lo <= hi, within +-32768) and
+ * sigma_min (finite, >= 0) are screened on the host. */
+#define MT_CEM_AUTO_RESET 0x1u   /* committed steps re-arm finished envs, as MT_TAPE_AUTO_RESET */
+#define MT_CEM_KEEP_MEAN  0x2u   /* candidate 0 is the clamped mean (z = 0) */
+struct mt_cem {            /* as with mt_shoot, the type is always written `struct mt_cem` */
+  int32_t struct_size;     /* = sizeof(struct mt_cem), checked */
+  int32_t n_steps;         /* T, 0..65535 */
+  int32_t n_candidates;    /* C, 1..64 */
+  int32_t n_elites;        /* E, 1..C */
+  int32_t commit_steps;    /* H, 0..T */
+  uint32_t draw;           /* major counter word of the plan stream (e.g. the iteration number) */
+  const float *mean, *sigma; int64_t ld;         /* DEVICE (T, D, ld), ld >= n_envs */
+  float *mean_out, *sigma_out; int64_t out_ld;   /* DEVICE or both NULL: the refit; may be EXACTLY mean / sigma with out_ld == ld */
+  float lo, hi, sigma_min;
+  float* returns_out; int64_t ret_ld;            /* DEVICE or NULL: (C, ret_ld) return of every candidate */
+  int32_t* best_out; float* best_return_out;     /* DEVICE or NULL (N,): as mt_shoot */
+  uint64_t* elite_mask_out;                      /* DEVICE or NULL (N,): bit c set iff candidate c is an elite of env i */
+  float* chosen_out; int64_t chosen_ld;          /* DEVICE (H, D, chosen_ld): steps 0..H-1 of each env's best candidate; required when H > 0 */
+  int8_t* reward_log; uint8_t* done_log; int64_t log_ld; float* return_out;   /* of the committed steps, as mt_shoot */
+  uint64_t seed;           /* keys the plan stream AND the re-armed envs' targets */
+  uint32_t flags, reserved;
+};
+MT_API int mt_cem(mt_handle h, const struct mt_cem* s);
+/* (plans_out is a void* like mt_get's destination: the block is output only, there is nothing to screen) */
+MT_API int mt_sample_plans(mt_handle h, const struct mt_cem* s, void* plans_out, int64_t ld, int64_t cand_stride);
 
 /* Environment.get_observations(), manytor.py:141-153, at the current pose (also
  * zeroes the coordinates of dead targets, :148).  Result in MT_F_OBS. */

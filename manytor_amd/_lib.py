@@ -124,6 +124,46 @@ class MtShoot(C.Structure):
 
 SHOOT_AUTO_RESET = 0x1
 
+
+
+class MtCem(C.Structure):
+    """struct mt_cem of include/manytor_hip.h: the argument block of mt_cem and mt_sample_plans."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_steps", C.c_int32),
+        ("n_candidates", C.c_int32),
+        ("n_elites", C.c_int32),
+        ("commit_steps", C.c_int32),
+        ("draw", C.c_uint32),
+        ("mean", C.c_void_p),
+        ("sigma", C.c_void_p),
+        ("ld", C.c_int64),
+        ("mean_out", C.c_void_p),
+        ("sigma_out", C.c_void_p),
+        ("out_ld", C.c_int64),
+        ("lo", C.c_float),
+        ("hi", C.c_float),
+        ("sigma_min", C.c_float),
+        ("returns_out", C.c_void_p),
+        ("ret_ld", C.c_int64),
+        ("best_out", C.c_void_p),
+        ("best_return_out", C.c_void_p),
+        ("elite_mask_out", C.c_void_p),
+        ("chosen_out", C.c_void_p),
+        ("chosen_ld", C.c_int64),
+        ("reward_log", C.c_void_p),
+        ("done_log", C.c_void_p),
+        ("log_ld", C.c_int64),
+        ("return_out", C.c_void_p),
+        ("seed", C.c_uint64),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+CEM_AUTO_RESET = 0x1
+CEM_KEEP_MEAN = 0x2
+
 _HANDLE = C.c_void_p
 
 # name -> (restype, argtypes); exactly the prototypes of include/manytor_hip.h
@@ -154,6 +194,8 @@ PROTOTYPES = {
     "mt_rollout_fused": (C.c_int, [_HANDLE, C.c_int, C.c_uint64, C.c_uint32, C.c_int]),
     "mt_rollout_tape": (C.c_int, [_HANDLE, C.POINTER(MtTape)]),
     "mt_shoot": (C.c_int, [_HANDLE, C.POINTER(MtShoot)]),
+    "mt_cem": (C.c_int, [_HANDLE, C.POINTER(MtCem)]),
+    "mt_sample_plans": (C.c_int, [_HANDLE, C.POINTER(MtCem), C.c_void_p, C.c_int64, C.c_int64]),
     "mt_observe": (C.c_int, [_HANDLE]),
     "mt_check_done": (C.c_int, [_HANDLE]),
     "mt_get": (C.c_int, [_HANDLE, C.c_int, C.c_void_p, C.c_int64, C.c_int]),

@@ -839,6 +839,29 @@ void launch_shoot(mt_handle h, const StepArgs& a, const ShootArgs& r) {
   MT_DISPATCH_D(h->D, launch_shoot_d, h, a, r);
 }
 
+// cem_kernel on the whole batch: shoot_kernel's shape plus the [C][64] score tile, the four waves' elite masks and the
+// best index (at most 43 KB: K = 32, C = 64).
+template <class Tbl>
+void launch_cem_t(mt_handle h, const StepArgs& a, const CemArgs& r) {
+  const size_t lds = ((size_t)3 * h->K + (size_t)r.C + 2 * kShootWaves + 1) * kShootEnvs * sizeof(float);
+  hipLaunchKernelGGL((cem_kernel<Tbl>), dim3((unsigned)((a.n + kShootEnvs - 1) / kShootEnvs)), dim3(kBlock), lds, h->stream, a, r);
+}
+template <int D>
+void launch_cem_d(mt_handle h, const StepArgs& a, const CemArgs& r) {
+  launch_cem_t<RtTable<D>>(h, a, r);
+}
+void launch_cem(mt_handle h, const StepArgs& a, const CemArgs& r) {
+  if (h->static_kind == 1) return launch_cem_t<Ref4Table>(h, a, r);
+  if (h->static_kind == 2) return launch_cem_t<Dh7Table>(h, a, r);
+  MT_DISPATCH_D(h->D, launch_cem_d, h, a, r);
+}
+// sample_plans_kernel: a thread per (env, step, candidate); it needs the number of joints only
+template <int D>
+void launch_sample_plans_d(mt_handle h, const CemArgs& r, float* plans, int64_t ld, int64_t cand_stride) {
+  hipLaunchKernelGGL((sample_plans_kernel<D>), dim3(grid_for(h->n).x, (unsigned)r.T, (unsigned)r.C), dim3(kBlock), 0, h->stream, r, plans,
+                     ld, cand_stride, h->args.n, h->args.env_base);
+}
+
 // The rollout kernels implement the default trigonometry and the reference's frame rows only.
 bool fusable(mt_handle h) { return h->trig == 0 && !h->lds_table && !h->trace && !h->custom_frames; }
 
@@ -1220,6 +1243,9 @@ const char* mt_describe_dispatch(mt_handle h) {
       ",\"nt_loads\":" + b(h->tape_nt_loads) + "}" +
       // mt_shoot: a block scores all candidates of 64 envs, one wave per candidate at a time
       ",\"shoot\":{\"usable\":" + b(fusable(h)) + ",\"envs_per_block\":" + num(kShootEnvs) + ",\"waves_per_block\":" + num(kShootWaves) + "}" +
+      // mt_cem: shoot's shape, the candidates drawn in the kernel
+      ",\"cem\":{\"usable\":" + b(fusable(h)) + ",\"envs_per_block\":" + num(kShootEnvs) + ",\"waves_per_block\":" + num(kShootWaves) +
+      ",\"max_candidates\":64}" +
       ",\"reset\":{\"lanes_per_env\":" + num(h->reset_split ? 4 : 1) + "}" +
       // the ground test's interior poses on dense lanes of the block: the step launches that take it (the single-env view,
       // the rollout, tape and shoot kernels never do)
@@ -2108,6 +2134,151 @@ int mt_shoot(mt_handle h, const struct mt_shoot* s) {
   h->args.flags &= ~kFlagWholeGoals;  // tape angles are anybody's floats
   h->codes_valid = false;             // the kernel writes targets as floats only
   return check_launch(h, "rollout_tape_kernel<SELECT>");
+}
+
+namespace {
+// what mt_cem and mt_sample_plans both read of a struct mt_cem: the candidate stream's parameters
+int cem_stream_args(mt_handle h, const struct mt_cem* s, const char* who, CemArgs& e) {
+  const std::string w(who);
+  MT_REQUIRE(h, s->n_steps >= 0 && s->n_steps <= 65535, w + ": mt_cem.n_steps must be 0..65535");
+  MT_REQUIRE(h, s->n_candidates >= 1 && s->n_candidates <= 64, w + ": mt_cem.n_candidates must be 1..64");
+  MT_REQUIRE(h, (s->flags & ~(MT_CEM_AUTO_RESET | MT_CEM_KEEP_MEAN)) == 0, w + ": mt_cem.flags: unknown MT_CEM_* flag");
+  // (bit patterns: the build is -ffinite-math-only; 0x47000000 = 32768.0f, the largest angle a step accepts)
+  MT_REQUIRE(h, first_unusable(&s->lo, 1, 0x47000000u) < 0 && first_unusable(&s->hi, 1, 0x47000000u) < 0,
+             w + ": mt_cem.lo / hi must be finite and within +-32768 degrees");
+  MT_REQUIRE(h, s->lo <= s->hi, w + ": mt_cem.lo must be <= hi");
+  e.mean = s->mean;
+  e.sigma = s->sigma;
+  e.ld = s->ld;
+  e.T = s->n_steps;
+  e.C = s->n_candidates;
+  e.draw = s->draw;
+  e.keep_mean = (s->flags & MT_CEM_KEEP_MEAN) ? 1u : 0u;
+  e.seed_lo = (uint32_t)s->seed;
+  e.seed_hi = (uint32_t)(s->seed >> 32);
+  e.lo = s->lo;
+  e.hi = s->hi;
+  return MT_OK;
+}
+// do [p, p + rows * ld) and [q, q + rows2 * ld2) share a byte?  (rows of n floats, the last one not padded)
+bool rows_overlap(const float* p, int64_t rows, int64_t ld, const float* q, int64_t rows2, int64_t ld2, int64_t n) {
+  if (!p || !q || rows == 0 || rows2 == 0) return false;
+  const uintptr_t a0 = (uintptr_t)p, a1 = a0 + (uintptr_t)(((rows - 1) * ld + n) * 4);
+  const uintptr_t b0 = (uintptr_t)q, b1 = b0 + (uintptr_t)(((rows2 - 1) * ld2 + n) * 4);
+  return a0 < b1 && b0 < a1;
+}
+}  // namespace
+
+int mt_sample_plans(mt_handle h, const struct mt_cem* s, void* plans_out, int64_t ld, int64_t cand_stride) {
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  MT_REQUIRE(h, s != nullptr, "mt_sample_plans: cem is NULL");
+  CemArgs e{};
+  int rc = cem_stream_args(h, s, "mt_sample_plans", e);
+  if (rc) return rc;
+  if (s->n_steps == 0) return MT_OK;
+  MT_REQUIRE(h, s->mean != nullptr && s->sigma != nullptr, "mt_sample_plans: mt_cem.mean / sigma is NULL");
+  MT_REQUIRE(h, s->ld >= h->n, "mt_sample_plans: mt_cem.ld is smaller than n_envs");
+  MT_REQUIRE(h, plans_out != nullptr, "mt_sample_plans: plans_out is NULL");
+  MT_REQUIRE(h, ld >= h->n, "mt_sample_plans: ld is smaller than n_envs");
+  MT_REQUIRE(h, cand_stride >= (int64_t)s->n_steps * h->D * ld, "mt_sample_plans: cand_stride is smaller than n_steps * dof * ld");
+  MT_ENTER(h);
+  MT_DISPATCH_D(h->D, launch_sample_plans_d, h, e, static_cast<float*>(plans_out), ld, cand_stride);
+  return check_launch(h, "sample_plans_kernel");
+}
+
+int mt_cem(mt_handle h, const struct mt_cem* s) {
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  MT_REQUIRE(h, s != nullptr, "cem is NULL");
+  MT_REQUIRE(h, s->struct_size == (int32_t)sizeof(struct mt_cem), "mt_cem.struct_size does not match this library");
+  MT_REQUIRE(h, s->reserved == 0, "mt_cem.reserved must be 0");
+  CemArgs e{};
+  int rc = cem_stream_args(h, s, "mt_cem", e);
+  if (rc) return rc;
+  const bool auto_reset = (s->flags & MT_CEM_AUTO_RESET) != 0;
+  const int T = s->n_steps, H = s->commit_steps;
+  MT_REQUIRE(h, s->n_elites >= 1 && s->n_elites <= s->n_candidates, "mt_cem.n_elites must be 1..n_candidates");
+  MT_REQUIRE(h, H >= 0 && H <= T, "mt_cem.commit_steps must be 0..n_steps");
+  MT_REQUIRE(h, !(auto_reset && H == 0), "MT_CEM_AUTO_RESET with mt_cem.commit_steps == 0: an evaluation re-arms nothing");
+  MT_REQUIRE(h, first_unusable(&s->sigma_min, 1, kMaxFiniteBits) < 0 && s->sigma_min >= 0.f, "mt_cem.sigma_min must be finite and >= 0");
+  if (!fusable(h)) {  // the rollout kernels do not implement these
+    const char* what = h->custom_frames ? "custom obs_frame / ee_frame"
+                       : h->trace       ? "MT_FLAG_TRACE"
+                       : h->lds_table   ? "MT_FLAG_DH_IN_LDS"
+                       : h->trig == 2   ? "MT_FLAG_HW_TRIG"
+                       : (h->cfg.flags & MT_FLAG_DIRECT_TRIG) ? "MT_FLAG_DIRECT_TRIG"
+                       : h->trig == 1   ? "substeps beyond the recurrence's reach (per-pose trigonometry)"
+                                        : "a profiling flag (MT_FLAG_ABLATE_*)";
+    return fail(h, MT_ERR_UNSUPPORTED, std::string("mt_cem: not available on a handle with ") + what);
+  }
+  if (!h->is_reset) return fail(h, MT_ERR_STATE, "mt_cem before mt_reset / mt_reset_random");
+  if (T == 0) return MT_OK;
+  const int64_t n = h->n, rows = (int64_t)T * h->D;
+  MT_REQUIRE(h, s->mean != nullptr && s->sigma != nullptr, "mt_cem.mean / sigma is NULL");
+  MT_REQUIRE(h, s->ld >= n, "mt_cem.ld is smaller than n_envs");
+  MT_REQUIRE(h, (s->mean_out == nullptr) == (s->sigma_out == nullptr), "mt_cem.mean_out and sigma_out: both or neither");
+  MT_REQUIRE(h, !s->mean_out || s->out_ld >= n, "mt_cem.out_ld is smaller than n_envs");
+  MT_REQUIRE(h, !s->returns_out || s->ret_ld >= n, "mt_cem.ret_ld is smaller than n_envs");
+  MT_REQUIRE(h, !(H > 0 && s->chosen_out == nullptr), "mt_cem.chosen_out is NULL with commit_steps > 0");
+  MT_REQUIRE(h, !(H > 0) || s->chosen_ld >= n, "mt_cem.chosen_ld is smaller than n_envs");
+  MT_REQUIRE(h, !(H > 0 && (s->reward_log || s->done_log)) || s->log_ld >= n, "mt_cem.log_ld is smaller than n_envs");
+  // the refit may sit EXACTLY on its input (same base, same pitch: every element is then read and written by one thread);
+  // any other overlap of an output with mean / sigma or with the other output would let one block read another's writes
+  const bool same_m = s->mean_out == s->mean && s->out_ld == s->ld, same_s = s->sigma_out == s->sigma && s->out_ld == s->ld;
+  MT_REQUIRE(h, same_m || !rows_overlap(s->mean_out, rows, s->out_ld, s->mean, rows, s->ld, n), "mt_cem.mean_out overlaps mean without being mean");
+  MT_REQUIRE(h, same_s || !rows_overlap(s->sigma_out, rows, s->out_ld, s->sigma, rows, s->ld, n), "mt_cem.sigma_out overlaps sigma without being sigma");
+  MT_REQUIRE(h, !rows_overlap(s->mean_out, rows, s->out_ld, s->sigma, rows, s->ld, n), "mt_cem.mean_out overlaps sigma");
+  MT_REQUIRE(h, !rows_overlap(s->sigma_out, rows, s->out_ld, s->mean, rows, s->ld, n), "mt_cem.sigma_out overlaps mean");
+  MT_REQUIRE(h, !rows_overlap(s->mean_out, rows, s->out_ld, s->sigma_out, rows, s->out_ld, n), "mt_cem.mean_out overlaps sigma_out");
+  if (H > 0) {
+    const int64_t hr = (int64_t)H * h->D;
+    MT_REQUIRE(h, !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->mean, rows, s->ld, n) &&
+                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->sigma, rows, s->ld, n) &&
+                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->mean_out, rows, s->out_ld, n) &&
+                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->sigma_out, rows, s->out_ld, n),
+               "mt_cem.chosen_out overlaps mean / sigma / mean_out / sigma_out");
+  }
+  MT_ENTER(h);
+  e.mean_out = s->mean_out;
+  e.sigma_out = s->sigma_out;
+  e.out_ld = s->out_ld;
+  e.returns_out = s->returns_out;
+  e.ret_ld = s->ret_ld;
+  e.best_out = s->best_out;
+  e.best_return_out = s->best_return_out;
+  e.elite_mask = reinterpret_cast<unsigned long long*>(s->elite_mask_out);
+  e.chosen_out = H > 0 ? s->chosen_out : nullptr;
+  e.chosen_ld = s->chosen_ld;
+  e.E = s->n_elites;
+  e.H = H;
+  e.sigma_min = s->sigma_min;
+  e.inv_e = 1.0f / (float)s->n_elites;  // the fp32 nearest to 1 / E
+  launch_cem(h, h->args, e);            // reads the state, writes the caller's rows only
+  rc = check_launch(h, "cem_kernel");
+  if (rc || H == 0) return rc;
+  // the commit: mt_rollout_tape(n_steps = H, actions = chosen_out), host bookkeeping included
+  if (auto_reset) {
+    h->args.seed_lo = (uint32_t)s->seed;
+    h->args.seed_hi = (uint32_t)(s->seed >> 32);
+    int rcg = order_behind_inplace_gather(h, h->stream);  // the in-kernel re-arm writes MT_F_LAST_RETURN
+    if (rcg) return rcg;
+  }
+  TapeArgs r{};
+  r.tape = s->chosen_out;
+  r.tape_ld = s->chosen_ld;
+  r.reward_log = s->reward_log;
+  r.done_log = s->done_log;
+  r.log_ld = s->log_ld;
+  r.return_out = s->return_out;
+  r.T = H;
+  r.auto_reset = auto_reset ? 1u : 0u;
+  r.nt_loads = h->tape_nt_loads ? 1u : 0u;
+  r.seed_lo = (uint32_t)s->seed;
+  r.seed_hi = (uint32_t)(s->seed >> 32);
+  r.radius = h->cfg.radius;
+  launch_tape(h, h->args, r);
+  h->args.flags &= ~kFlagWholeGoals;  // drawn angles are anybody's floats
+  h->codes_valid = false;             // the kernel writes targets as floats only
+  return check_launch(h, "rollout_tape_kernel");
 }
 
 int mt_observe(mt_handle h) {

@@ -2630,6 +2630,235 @@ __global__ __launch_bounds__(kBlock) void shoot_kernel(const StepArgs a, const S
 }
 
 // ---------------------------------------------------------------------------
+// mt_cem: one iteration of the cross-entropy method where the data sits.  The candidates shoot_kernel reads from a
+// (C, T, D, N) block are DRAWN here -- a candidate angle is a pure function of (seed, global env id, draw, c, t, j) and
+// of the env's mean and sigma (philox.h: the plan stream) -- so the block never exists; mt_sample_plans
+// (sample_plans_kernel) writes it out for whoever wants it, and the evaluation below equals shoot_kernel on that block
+// bit for bit: same block / wave / lane shape (a wave = 64 consecutive envs of ONE candidate), same step.
+//   an angle : x = mean + sigma * z (two roundings; contraction is off); unusable_angle(x) is handed on as it is (the
+//              step holds the pose), anything else is clamped to [lo, hi].  KEEP_MEAN: candidate 0 has z = 0.
+//   scores   : every candidate's return goes into a [C][64] LDS tile as well.  Behind the barrier each wave ranks ITS
+//              candidates against the tile (rank = number of candidates that beat it: a higher return, or the same
+//              return and a lower index; a lane reads its own column: conflict-free), sets the bits of those with
+//              rank < E in its own [64] mask row and names the one with rank 0 (exactly one per env) as best.
+//   refit    : behind a second barrier the waves split the T steps.  For step t a lane regenerates the angles of its E
+//              elites in ascending index order (lowest set bit first) -- twice, first for the mean, then for the squared
+//              deviations, nothing is stored -- and writes mean_out / sigma_out[t][.][i].  With mean_out == mean the
+//              element is read and written by this one thread, after the block's last scoring read.  The same pass
+//              writes rows t < H of chosen_out from the best candidate.
+// No atomics on global memory, no init pass, no dependence between blocks.  Tail lanes meet every barrier and store nothing.
+// ---------------------------------------------------------------------------
+struct CemArgs {
+  const float *mean, *sigma;  // [T * D][ld]
+  int64_t ld;
+  float *mean_out, *sigma_out;  // [T * D][out_ld] or both NULL
+  int64_t out_ld;
+  float* returns_out;  // [C][ret_ld] or NULL
+  int64_t ret_ld;
+  int32_t* best_out;               // [n] or NULL
+  float* best_return_out;          // [n] or NULL
+  unsigned long long* elite_mask;  // [n] or NULL
+  float* chosen_out;               // [H * D][chosen_ld] or NULL (H == 0)
+  int64_t chosen_ld;
+  int32_t T, C, E, H;
+  uint32_t draw, keep_mean;
+  uint32_t seed_lo, seed_hi;
+  float lo, hi, sigma_min, inv_e;
+};
+
+// the D angles of candidate c at step t from the env's mean / sigma rows of that step
+template <int D>
+__device__ __forceinline__ void plan_angles(const CemArgs& r, uint64_t seed, uint64_t env_id, uint32_t c, uint32_t t,
+                                            const float (&mu)[D], const float (&sg)[D], float (&x)[D]) {
+  static_assert(D <= 8, "a plan step is at most two Philox blocks");
+  const bool zero = (r.keep_mean != 0u) & (c == 0u);
+  const u32x4 b0 = stream_block(seed, env_id, kTagPlan, r.draw, plan_minor(c, 0u, t));
+  uint32_t w[8] = {b0.x, b0.y, b0.z, b0.w, 0u, 0u, 0u, 0u};
+  if constexpr (D > 4) {
+    const u32x4 b1 = stream_block(seed, env_id, kTagPlan, r.draw, plan_minor(c, 1u, t));
+    w[4] = b1.x;
+    w[5] = b1.y;
+    w[6] = b1.z;
+    w[7] = b1.w;
+  }
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    const float z = zero ? 0.f : plan_noise(w[j]);
+    const float sz = sg[j] * z;
+    const float v = mu[j] + sz;
+    x[j] = unusable_angle(v) ? v : fminf(fmaxf(v, r.lo), r.hi);
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void sample_plans_kernel(const CemArgs r, float* plans, int64_t ld, int64_t cand_stride, int64_t n,
+                                                              int64_t env_base) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t t = blockIdx.y, c = blockIdx.z;
+  LaneOffset<true> o4{i * 4u};
+  const uint64_t seed = ((uint64_t)r.seed_hi << 32) | r.seed_lo;
+  float mu[D], sg[D], x[D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    mu[j] = tape_load(r.mean + ((int64_t)t * D + j) * r.ld, o4, false);
+    sg[j] = tape_load(r.sigma + ((int64_t)t * D + j) * r.ld, o4, false);
+  }
+  plan_angles<D>(r, seed, (uint64_t)(env_base + i), c, t, mu, sg, x);
+  float* plane = plans + (int64_t)c * cand_stride;
+#pragma unroll
+  for (int j = 0; j < D; ++j) str_stream(plane + ((int64_t)t * D + j) * ld, o4, x[j]);
+}
+
+template <class Tbl>
+__global__ __launch_bounds__(kBlock) void cem_kernel(const StepArgs a, const CemArgs r) {
+  // [3K][64] targets, [C][64] returns, [4][64] 64-bit elite masks (one row per wave), [64] best indices
+  extern __shared__ __attribute__((aligned(16))) float tile[];
+  constexpr int D = Tbl::D;
+  const Tbl t = TableMaker<Tbl>::make(a.dh);
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t i = blockIdx.x * kShootEnvs + lane;
+  const bool live = i < a.n;
+  LaneOffset<true> o4{i * 4u};
+  const int64_t ld = a.ld;
+  const float* col = tile + lane;
+  float* rets = tile + 3 * a.K * kShootEnvs;
+  unsigned long long* masks = reinterpret_cast<unsigned long long*>(rets + r.C * kShootEnvs);
+  int32_t* best_c = reinterpret_cast<int32_t*>(masks + kShootWaves * kShootEnvs);
+  const uint64_t seed = ((uint64_t)r.seed_hi << 32) | r.seed_lo;
+  const uint64_t env_id = (uint64_t)(a.env_base + i);
+
+  float g0[D];
+  uint32_t am0 = 0u;
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) g0[j] = ldr(a.goals + j * ld, o4);
+    am0 = ldr(a.alive, o4);
+    for (int k = (int)w; k < 3 * a.K; k += kShootWaves) tile[k * kShootEnvs + lane] = ldr(a.points + (int64_t)k * ld, o4);
+  }
+  __syncthreads();
+
+  // ---- score: shoot_kernel's loop with the drawn angles in place of the tape's ----
+  if (live) {
+    for (int c = (int)w; c < r.C; c += kShootWaves) {  // (wave-uniform)
+      float g[D];
+#pragma unroll
+      for (int j = 0; j < D; ++j) g[j] = g0[j];
+      uint32_t am = am0;
+      float ret = 0.f;
+      PoseCache<D> pose;
+      bool pose_valid = false;
+      for (int s = 0; s < r.T; ++s) {
+        float act[D], raw[D], mu[D], sg[D], el[3], e[3];
+#pragma unroll
+        for (int j = 0; j < D; ++j) {  // requested at the head of the step: the Philox rounds below cover the latency
+          mu[j] = tape_load(r.mean + ((int64_t)s * D + j) * r.ld, o4, false);
+          sg[j] = tape_load(r.sigma + ((int64_t)s * D + j) * r.ld, o4, false);
+        }
+        plan_angles<D>(r, seed, env_id, (uint32_t)c, (uint32_t)s, mu, sg, raw);
+        bool bad = false;
+#pragma unroll
+        for (int j = 0; j < D; ++j) bad |= unusable_angle(raw[j]);
+#pragma unroll
+        for (int j = 0; j < D; ++j) act[j] = bad ? g[j] : raw[j];  // the env holds its pose this step
+
+        const float zmin = route_kinematics<Tbl, 0, true, false>(t, a.S, a.inv_sm1, g, act, el, e, &pose, pose_valid, nullptr, false);
+        pose_valid = true;
+        const bool ground = zmin < 0.f;
+        uint32_t nam = am;
+        for (int k = 0; k < a.K; ++k) {
+          if (!((am >> k) & 1u)) continue;
+          const float* pk = col + 3 * k * kShootEnvs;
+          if (within_box(e, pk[0], pk[kShootEnvs], pk[2 * kShootEnvs], a.tol)) nam &= ~(1u << k);
+        }
+        ret += (float)(ground ? -1 : ((nam != am) ? 1 : 0));
+        am = nam;
+#pragma unroll
+        for (int j = 0; j < D; ++j) g[j] = act[j];
+      }
+      if (r.returns_out) str_stream(r.returns_out + (int64_t)c * r.ret_ld, o4, ret);
+      rets[c * kShootEnvs + lane] = ret;
+    }
+  }
+  __syncthreads();
+
+  // ---- rank this wave's candidates against all C ----
+  unsigned long long mine = 0ull;
+  if (live) {
+    for (int c = (int)w; c < r.C; c += kShootWaves) {
+      const float v = rets[c * kShootEnvs + lane];
+      int rank = 0;
+      for (int q = 0; q < r.C; ++q) {
+        const float u = rets[q * kShootEnvs + lane];
+        rank += ((u > v) | ((u == v) & (q < c))) ? 1 : 0;
+      }
+      if (rank < r.E) mine |= 1ull << c;
+      if (rank == 0) best_c[lane] = c;
+    }
+  }
+  masks[w * kShootEnvs + lane] = mine;
+  __syncthreads();
+  if (!live) return;  // (no barrier below)
+
+  unsigned long long elite = 0ull;
+#pragma unroll
+  for (int q = 0; q < kShootWaves; ++q) elite |= masks[q * kShootEnvs + lane];
+  const int32_t top_c = best_c[lane];
+  if (w == 0) {
+    if (r.best_out) str(r.best_out, o4, top_c);
+    if (r.best_return_out) str_stream(r.best_return_out, o4, rets[top_c * kShootEnvs + lane]);
+    if (r.elite_mask) r.elite_mask[i] = elite;
+  }
+
+  // ---- refit and the chosen rows: the waves split the steps ----
+  const bool refit = r.mean_out != nullptr;
+  for (int s = (int)w; s < r.T; s += kShootWaves) {  // (wave-uniform)
+    const bool pick = s < r.H;
+    if (!refit && !pick) break;  // (H <= T and s ascends: nothing further down either)
+    float mu[D], sg[D], x[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      mu[j] = tape_load(r.mean + ((int64_t)s * D + j) * r.ld, o4, false);
+      sg[j] = tape_load(r.sigma + ((int64_t)s * D + j) * r.ld, o4, false);
+    }
+    if (pick) {
+      plan_angles<D>(r, seed, env_id, (uint32_t)top_c, (uint32_t)s, mu, sg, x);
+#pragma unroll
+      for (int j = 0; j < D; ++j) str(r.chosen_out + ((int64_t)s * D + j) * r.chosen_ld, o4, x[j]);
+    }
+    if (!refit) continue;
+    float m[D] = {}, v[D] = {};  // (both overwritten by the first elite: the sums start from x_0 and d_0 * d_0)
+    unsigned long long left = elite;
+    for (int k = 0; k < r.E; ++k) {  // every live lane has exactly E elites; each lane walks its own, lowest index first
+      const uint32_t c = (uint32_t)__builtin_ctzll(left);
+      left &= left - 1ull;
+      plan_angles<D>(r, seed, env_id, c, (uint32_t)s, mu, sg, x);
+#pragma unroll
+      for (int j = 0; j < D; ++j) m[j] = (k == 0) ? x[j] : m[j] + x[j];
+    }
+#pragma unroll
+    for (int j = 0; j < D; ++j) m[j] = m[j] * r.inv_e;
+    left = elite;
+    for (int k = 0; k < r.E; ++k) {
+      const uint32_t c = (uint32_t)__builtin_ctzll(left);
+      left &= left - 1ull;
+      plan_angles<D>(r, seed, env_id, c, (uint32_t)s, mu, sg, x);
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        const float d = x[j] - m[j];
+        const float dd = d * d;
+        v[j] = (k == 0) ? dd : v[j] + dd;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      str(r.mean_out + ((int64_t)s * D + j) * r.out_ld, o4, m[j]);
+      str(r.sigma_out + ((int64_t)s * D + j) * r.out_ld, o4, fmaxf(sqrtf(v[j] * r.inv_e), r.sigma_min));
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // get_observations() at the current pose (manytor.py:141-153).
 // ---------------------------------------------------------------------------
 template <int D>

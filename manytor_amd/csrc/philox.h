@@ -15,6 +15,7 @@ namespace mt {
 
 constexpr uint32_t kTagAction = 1u;
 constexpr uint32_t kTagTarget = 2u;
+constexpr uint32_t kTagPlan = 3u;  // mt_cem / mt_sample_plans: the noise of candidate plans
 
 struct u32x4 {
   uint32_t x, y, z, w;
@@ -72,6 +73,22 @@ __host__ __device__ __forceinline__ void candidate_fields(const u32x4& w, uint32
     fy = ((w.y & 0x7FFu) << 10) | ((w.w >> 12) & 0x3FFu);
     fz = ((w.z & 0x7FFu) << 10) | ((w.w >> 2) & 0x3FFu);
   }
+}
+
+// The plan stream (mt_cem, mt_sample_plans): candidate c of env e at step t of draw `draw` takes its noise from
+//   stream_block(seed, e, kTagPlan, major = draw, minor = (c << 24) | (b << 16) | t),   b = 0: joints 0..3, b = 1: joints 4..7
+// one word per joint.  A word becomes z = (sum of its four bytes - 510) * kPlanNoiseScale: Irwin-Hall of four uniform bytes,
+// mean 0, variance 4 (256^2 - 1) / 12 = 21 845 before the scale, |z| <= 3.4506.  Everything before the multiply is exact
+// in fp32, so the multiply is the only rounding and tests/cem_ref.py restates it bit for bit.
+constexpr float kPlanNoiseScale = 0x1.bb688cp-8f;  // the fp32 nearest to 1 / sqrt(21845)
+__host__ __device__ __forceinline__ uint32_t plan_minor(uint32_t c, uint32_t b, uint32_t t) { return (c << 24) | (b << 16) | t; }
+__host__ __device__ __forceinline__ float plan_noise(uint32_t w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t s = __builtin_amdgcn_sad_u8(w, 0u, 0u);  // v_sad_u8 against 0: the sum of the four bytes
+#else
+  const uint32_t s = (w & 0xFFu) + ((w >> 8) & 0xFFu) + ((w >> 16) & 0xFFu) + (w >> 24);
+#endif
+  return (float)((int32_t)s - 510) * kPlanNoiseScale;
 }
 
 }  // namespace mt

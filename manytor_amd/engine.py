@@ -497,6 +497,144 @@ class StepEngine:
             self.version += 1
         return out
 
+    def _cem_rows(self, mean, sigma):
+        """(mean, sigma, T, ld) of mt_cem's inputs: CUDA float32 (T, D, N) tensors on the engine's device with unit env
+        stride and ONE uniform row pitch >= N, read in place.  Nothing is copied: the refit may be written onto them."""
+        import torch
+        n, d = self.n_envs, self.dof
+        dev = torch.device("cuda", self.device)
+        for name, t in (("mean", mean), ("sigma", sigma)):
+            if not _is_torch_tensor(t) or not t.is_cuda or t.device != dev or t.dtype != torch.float32:
+                raise ValueError(f"{name} must be a CUDA float32 tensor on the engine's device")
+            if t.dim() != 3 or tuple(t.shape[1:]) != (d, n):
+                raise ValueError(f"{name} must be (T, {d}, {n}), got {tuple(t.shape)}")
+        if mean.shape[0] != sigma.shape[0]:
+            raise ValueError("mean and sigma must cover the same number of steps")
+        T = int(mean.shape[0])
+        if T > 65535:
+            raise ValueError(f"at most 65535 steps, got {T}")
+        if T == 0:
+            return mean, sigma, 0, n
+        ld = int(mean.stride(1))
+        for name, t in (("mean", mean), ("sigma", sigma)):
+            if t.stride(2) != 1 or t.stride(1) != ld or ld < n or t.stride(0) != d * ld:
+                raise ValueError(f"{name} must have unit env stride and the row pitch of mean (>= N), rows (t, j) in order")
+        return mean, sigma, T, ld
+
+    @staticmethod
+    def _cem_scalars(candidates, lo, hi):
+        c, lo, hi = int(candidates), float(lo), float(hi)
+        if not 1 <= c <= 64:
+            raise ValueError(f"candidates must be 1..64, got {c}")
+        if not (np.isfinite(lo) and np.isfinite(hi) and -32768.0 <= lo <= hi <= 32768.0):
+            raise ValueError(f"lo <= hi must be finite and within +-32768 degrees, got {lo}, {hi}")
+        return c, lo, hi
+
+    def sample_plans(self, mean, sigma, *, candidates, draw=0, seed=0x5EED, lo=-180., hi=180., keep_mean=False):
+        """The (C, T, D, N) float32 block of candidate plans that cem() with the same arguments scores (mt_sample_plans):
+        x = mean + sigma * z, clamped to [lo, hi], z the library's counter-based noise keyed by (seed, global env id, draw,
+        candidate, step, joint).  `mean` and `sigma` are CUDA float32 (T, D, N) tensors read in place.  Stream rules as
+        shoot()."""
+        import torch
+        c, lo, hi = self._cem_scalars(candidates, lo, hi)
+        mean, sigma, T, ld = self._cem_rows(mean, sigma)
+        n, d = self.n_envs, self.dof
+        out = torch.empty((c, T, d, n), dtype=torch.float32, device=mean.device)
+        arg = L.MtCem()
+        arg.struct_size = C.sizeof(L.MtCem)
+        arg.n_steps, arg.n_candidates, arg.draw = T, c, int(draw) & 0xFFFFFFFF
+        arg.mean, arg.sigma, arg.ld = (mean.data_ptr(), sigma.data_ptr(), ld) if T else (None, None, n)
+        arg.lo, arg.hi = lo, hi
+        arg.seed = int(seed)
+        arg.flags = L.CEM_KEEP_MEAN if keep_mean else 0
+        cur = int(torch.cuda.current_stream(self.device).cuda_stream)
+        ordered = getattr(self, "_caller_stream", None) == cur
+        if not ordered:
+            torch.cuda.current_stream(self.device).synchronize()
+        self._call(self._lib.mt_sample_plans, C.byref(arg), C.c_void_p(out.data_ptr() if T else None), C.c_int64(n),
+                   C.c_int64(T * d * n))
+        if not ordered:
+            self.sync()
+        return out
+
+    def cem(self, mean, sigma, *, candidates, elites, draw=0, seed=0x5EED, commit=0, auto_reset=False, lo=-180., hi=180.,
+            sigma_min=0., keep_mean=False, inplace=False, all_returns=False, elite_mask=False, log=False, returns=False):
+        """One iteration of the cross-entropy method in one call (mt_cem): C = `candidates` plans per env are DRAWN in the
+        kernel around `mean` / `sigma` (CUDA float32 (T, D, N), read in place; the block is what sample_plans() returns for
+        the same arguments, but it never exists), scored exactly as shoot() scores them, and (mean, sigma) are refitted from
+        each env's E = `elites` best (return descending, index ascending).  Returns a dict of device tensors: `best` (N,)
+        int32, `best_return` (N,) float32, `mean` / `sigma` (T, D, N) -- new tensors, or with inplace=True the arguments
+        themselves, overwritten -- plus `candidate_returns` (C, N) with all_returns=True and `elite_mask` (N,) int64 (bit c
+        = candidate c is an elite) with elite_mask=True.  commit=H > 0 also executes steps 0..H-1 of each env's best plan
+        for real, as rollout_actions(chosen, layout="soa", auto_reset=, seed=) would: `chosen` (H, D, N) holds those
+        angles, log=True adds `reward` / `done` (H, N) and returns=True `returns` (N,).  sigma is floored at sigma_min;
+        keep_mean=True makes candidate 0 the clamped mean.  Stream rules as shoot(); with commit == 0 nothing resident
+        changes."""
+        import torch
+        commit = int(commit)
+        if auto_reset and commit == 0:
+            raise ValueError("auto_reset needs commit > 0: an evaluation re-arms nothing")
+        c, lo, hi = self._cem_scalars(candidates, lo, hi)
+        e, sigma_min = int(elites), float(sigma_min)
+        if not 1 <= e <= c:
+            raise ValueError(f"elites must be 1..candidates = {c}, got {e}")
+        if not (np.isfinite(sigma_min) and sigma_min >= 0.0):
+            raise ValueError(f"sigma_min must be finite and >= 0, got {sigma_min}")
+        mean, sigma, T, ld = self._cem_rows(mean, sigma)
+        if not 0 <= commit <= T:
+            raise ValueError(f"commit must be 0..T = {T}, got {commit}")
+        n, d = self.n_envs, self.dof
+        dev = mean.device
+        alloc = torch.empty if T else torch.zeros                # (T == 0: the call is a no-op and writes nothing)
+        out = {"best": alloc(n, dtype=torch.int32, device=dev), "best_return": alloc(n, dtype=torch.float32, device=dev)}
+        if inplace:
+            out["mean"], out["sigma"], out_ld = mean, sigma, ld
+        else:
+            out["mean"], out["sigma"], out_ld = torch.empty((T, d, n), dtype=torch.float32, device=dev), \
+                torch.empty((T, d, n), dtype=torch.float32, device=dev), n
+        if all_returns:
+            out["candidate_returns"] = alloc((c, n), dtype=torch.float32, device=dev)
+        if elite_mask:
+            out["elite_mask"] = alloc(n, dtype=torch.int64, device=dev)
+        if commit:
+            out["chosen"] = torch.empty((commit, d, n), dtype=torch.float32, device=dev)
+        if log:
+            out["reward"] = torch.empty((commit, n), dtype=torch.int8, device=dev)
+            out["done"] = torch.empty((commit, n), dtype=torch.uint8, device=dev)
+        if returns:
+            out["returns"] = (alloc if commit else torch.zeros)(n, dtype=torch.float32, device=dev)
+        arg = L.MtCem()
+        arg.struct_size = C.sizeof(L.MtCem)
+        arg.n_steps, arg.n_candidates, arg.n_elites, arg.commit_steps = T, c, e, commit
+        arg.draw = int(draw) & 0xFFFFFFFF
+        arg.mean, arg.sigma, arg.ld = (mean.data_ptr(), sigma.data_ptr(), ld) if T else (None, None, n)
+        arg.mean_out, arg.sigma_out, arg.out_ld = (out["mean"].data_ptr(), out["sigma"].data_ptr(), out_ld) if T else (None, None, n)
+        arg.lo, arg.hi, arg.sigma_min = lo, hi, sigma_min
+        arg.returns_out = out["candidate_returns"].data_ptr() if all_returns else None
+        arg.ret_ld = n
+        arg.best_out = out["best"].data_ptr()
+        arg.best_return_out = out["best_return"].data_ptr()
+        arg.elite_mask_out = out["elite_mask"].data_ptr() if elite_mask else None
+        arg.chosen_out = out["chosen"].data_ptr() if commit else None
+        arg.chosen_ld = n
+        arg.reward_log = out["reward"].data_ptr() if log and commit else None
+        arg.done_log = out["done"].data_ptr() if log and commit else None
+        arg.log_ld = n
+        arg.return_out = out["returns"].data_ptr() if returns and commit else None
+        arg.seed = int(seed)
+        arg.flags = (L.CEM_AUTO_RESET if auto_reset else 0) | (L.CEM_KEEP_MEAN if keep_mean else 0)
+        arg.reserved = 0
+        cur = int(torch.cuda.current_stream(self.device).cuda_stream)
+        ordered = getattr(self, "_caller_stream", None) == cur   # the engine launches on torch's current stream
+        if not ordered:
+            torch.cuda.current_stream(self.device).synchronize()
+        self._call(self._lib.mt_cem, C.byref(arg))
+        if not ordered:
+            self.sync()     # mean, sigma and the outputs are torch's memory: done with before torch may reuse or read it
+        if commit and T:
+            self.version += 1
+        return out
+
     def observe(self):
         """Environment.get_observations (manytor.py:141-153); result in field OBS."""
         self._call(self._lib.mt_observe)
