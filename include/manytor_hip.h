@@ -40,7 +40,7 @@ extern "C" {
 #define MT_API
 #endif
 
-#define MT_VERSION 420          /* major*10000 + minor*100 + patch */
+#define MT_VERSION 430          /* major*10000 + minor*100 + patch */
 #define MT_MAX_DOF 8
 #define MT_MAX_TARGETS 32
 #define MT_MAX_RETURN_RING 64
@@ -363,6 +363,60 @@ struct mt_cem {            /* as with mt_shoot, the type is always written `stru
 MT_API int mt_cem(mt_handle h, const struct mt_cem* s);
 /* (plans_out is a void* like mt_get's destination: the block is output only, there is nothing to screen) */
 MT_API int mt_sample_plans(mt_handle h, const struct mt_cem* s, void* plans_out, int64_t ld, int64_t cand_stride);
+
+/* One MPPI (model-predictive path integral) iteration in one call: draw C candidate plans per env around (mean, sigma),
+ * score them as mt_shoot does, weigh EVERY candidate by exp((R_c - R_best) / lambda), refit the mean (and on request sigma)
+ * as the weighted moments of the candidates and (commit_steps = H > 0) execute the first H steps of the best plan.  No
+ * (C, T, D, N) block exists, and no transcendental function is evaluated: a step's reward is -1, 0 or +1, so a return over
+ * T steps is an integer in [-T, T], the gap to the best return an integer k in [0, 2T], and with decay = rho =
+ * exp(-1 / lambda) the weight is rho^k, read from a table of 2T + 1 powers.
+ *
+ * mt_mppi, with P the block mt_sample_plans writes for a struct mt_cem with the same n_steps, n_candidates, draw, mean,
+ * sigma, ld, lo, hi, seed and KEEP_MEAN (the same Philox tag 3, counter and rounding: there is no new stream):
+ *   evaluation  returns_out, best_out, best_return_out are, bit for bit, what mt_shoot writes for actions = P (the lowest
+ *               index wins a tie; nothing resident changes; a refused angle is not counted).
+ *   weights     W[0] = 1, W[k] = W[k-1] * decay for k <= 2T, one fp32 rounding per entry; k_c = (int)(best_return - R_c),
+ *               exact because both are integer-valued; w_c = W[k_c]; weights_out[c*w_ld + i] = w_c.  decay = 0 is the
+ *               hard maximum (only candidates tied with the best count), decay = 1 the plain average.
+ *   refit       in fp32, one rounding per operation; every sum starts from +0 and takes c = 0, 1, ..., C-1 in order.
+ *               With x_c = P[c][t][j][i]:  S = sum of w_c;  A = sum of fl(w_c * x_c);  m = A / S (one correctly rounded
+ *               division);  mean_out = m.  With sigma_out: d_c = x_c - m, Q = sum of fl(w_c * fl(d_c * d_c)),
+ *               sigma_out = max(sqrt(Q / S), sigma_min).  weight_sum_out[i] = S; S >= 1, the best candidate weighs 1.
+ *               (A term whose weight is 0 may be skipped: with finite x it adds +-0 to a sum that started from +0.)
+ *               mean_out alone is a fixed-sigma MPPI; both, or neither, are allowed; sigma_out without mean_out is refused.
+ *               mean_out / sigma_out may be EXACTLY mean / sigma (same pointer, out_ld == ld): the refit is then in place.
+ *               Any other overlap of mean_out / sigma_out / chosen_out with mean / sigma or each other is refused.
+ *               The refit of env i is unspecified when its mean or sigma is non-finite or any of its drawn angles is
+ *               unusable; no other env's outputs change.
+ *   commit      chosen_out[(t*D + j)*chosen_ld + i] = P[best[i]][t][j][i] for t < H, and the handle is afterwards where
+ *               mt_rollout_tape(n_steps = H, actions = chosen_out, the same seed, MT_TAPE_AUTO_RESET iff MT_MPPI_AUTO_RESET)
+ *               leaves it: every field, the logs, return_out, mt_bad_action_count.
+ * At most two launches on the handle's stream, no allocation, no host wait: legal under stream capture.
+ * MT_ERR_UNSUPPORTED / MT_ERR_STATE as mt_cem; n_steps == 0 is a no-op; lo, hi (finite, lo <= hi, within +-32768),
+ * sigma_min (finite, >= 0) and decay (finite, 0 <= decay <= 1) are screened on the host. */
+#define MT_MPPI_AUTO_RESET 0x1u   /* committed steps re-arm finished envs, as MT_TAPE_AUTO_RESET */
+#define MT_MPPI_KEEP_MEAN  0x2u   /* candidate 0 is the clamped mean (z = 0), as MT_CEM_KEEP_MEAN */
+#define MT_MPPI_MAX_STEPS  127    /* 2T + 1 <= 255 table entries: every possible gap has its own weight, no clamp */
+struct mt_mppi {           /* as with mt_cem, the type is always written `struct mt_mppi` */
+  int32_t struct_size;     /* = sizeof(struct mt_mppi), checked */
+  int32_t n_steps;         /* T, 0..MT_MPPI_MAX_STEPS */
+  int32_t n_candidates;    /* C, 1..64 */
+  int32_t commit_steps;    /* H, 0..T */
+  uint32_t draw;           /* major counter word of the plan stream (e.g. the iteration number) */
+  float decay;             /* rho = exp(-1 / lambda), finite, 0 <= rho <= 1 */
+  const float *mean, *sigma; int64_t ld;         /* DEVICE (T, D, ld), ld >= n_envs */
+  float *mean_out, *sigma_out; int64_t out_ld;   /* DEVICE or NULL: the refit (mean_out alone, both, or neither); may be EXACTLY mean / sigma with out_ld == ld */
+  float lo, hi, sigma_min;
+  float* returns_out; int64_t ret_ld;            /* DEVICE or NULL: (C, ret_ld) return of every candidate */
+  float* weights_out; int64_t w_ld;              /* DEVICE or NULL: (C, w_ld) weight of every candidate */
+  float* weight_sum_out;                         /* DEVICE or NULL (N,): S, the sum of env i's weights */
+  int32_t* best_out; float* best_return_out;     /* DEVICE or NULL (N,): as mt_shoot */
+  float* chosen_out; int64_t chosen_ld;          /* DEVICE (H, D, chosen_ld): steps 0..H-1 of each env's best candidate; required when H > 0 */
+  int8_t* reward_log; uint8_t* done_log; int64_t log_ld; float* return_out;   /* of the committed steps, as mt_shoot */
+  uint64_t seed;           /* keys the plan stream AND the re-armed envs' targets */
+  uint32_t flags, reserved;
+};
+MT_API int mt_mppi(mt_handle h, const struct mt_mppi* s);
 
 /* Environment.get_observations(), manytor.py:141-153, at the current pose (also
  * zeroes the coordinates of dead targets, :148).  Result in MT_F_OBS. */

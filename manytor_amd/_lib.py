@@ -164,6 +164,48 @@ class MtCem(C.Structure):
 CEM_AUTO_RESET = 0x1
 CEM_KEEP_MEAN = 0x2
 
+
+class MtMppi(C.Structure):
+    """struct mt_mppi of include/manytor_hip.h: the argument block of mt_mppi."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_steps", C.c_int32),
+        ("n_candidates", C.c_int32),
+        ("commit_steps", C.c_int32),
+        ("draw", C.c_uint32),
+        ("decay", C.c_float),
+        ("mean", C.c_void_p),
+        ("sigma", C.c_void_p),
+        ("ld", C.c_int64),
+        ("mean_out", C.c_void_p),
+        ("sigma_out", C.c_void_p),
+        ("out_ld", C.c_int64),
+        ("lo", C.c_float),
+        ("hi", C.c_float),
+        ("sigma_min", C.c_float),
+        ("returns_out", C.c_void_p),
+        ("ret_ld", C.c_int64),
+        ("weights_out", C.c_void_p),
+        ("w_ld", C.c_int64),
+        ("weight_sum_out", C.c_void_p),
+        ("best_out", C.c_void_p),
+        ("best_return_out", C.c_void_p),
+        ("chosen_out", C.c_void_p),
+        ("chosen_ld", C.c_int64),
+        ("reward_log", C.c_void_p),
+        ("done_log", C.c_void_p),
+        ("log_ld", C.c_int64),
+        ("return_out", C.c_void_p),
+        ("seed", C.c_uint64),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+MPPI_AUTO_RESET = 0x1
+MPPI_KEEP_MEAN = 0x2
+MPPI_MAX_STEPS = 127
+
 _HANDLE = C.c_void_p
 
 # name -> (restype, argtypes); exactly the prototypes of include/manytor_hip.h
@@ -196,6 +238,7 @@ PROTOTYPES = {
     "mt_shoot": (C.c_int, [_HANDLE, C.POINTER(MtShoot)]),
     "mt_cem": (C.c_int, [_HANDLE, C.POINTER(MtCem)]),
     "mt_sample_plans": (C.c_int, [_HANDLE, C.POINTER(MtCem), C.c_void_p, C.c_int64, C.c_int64]),
+    "mt_mppi": (C.c_int, [_HANDLE, C.POINTER(MtMppi)]),
     "mt_observe": (C.c_int, [_HANDLE]),
     "mt_check_done": (C.c_int, [_HANDLE]),
     "mt_get": (C.c_int, [_HANDLE, C.c_int, C.c_void_p, C.c_int64, C.c_int]),

@@ -855,6 +855,22 @@ void launch_cem(mt_handle h, const StepArgs& a, const CemArgs& r) {
   if (h->static_kind == 2) return launch_cem_t<Dh7Table>(h, a, r);
   MT_DISPATCH_D(h->D, launch_cem_d, h, a, r);
 }
+// mppi_kernel on the whole batch: cem_kernel's shape; LDS holds the target tile, the [C][64] score / weight tile and the
+// table of 2T + 1 <= 255 powers of decay (at most 41 KB: K = 32, C = 64).
+template <class Tbl>
+void launch_mppi_t(mt_handle h, const StepArgs& a, const MppiArgs& r) {
+  const size_t lds = (((size_t)3 * h->K + (size_t)r.C) * kShootEnvs + kMppiTable) * sizeof(float);
+  hipLaunchKernelGGL((mppi_kernel<Tbl>), dim3((unsigned)((a.n + kShootEnvs - 1) / kShootEnvs)), dim3(kBlock), lds, h->stream, a, r);
+}
+template <int D>
+void launch_mppi_d(mt_handle h, const StepArgs& a, const MppiArgs& r) {
+  launch_mppi_t<RtTable<D>>(h, a, r);
+}
+void launch_mppi(mt_handle h, const StepArgs& a, const MppiArgs& r) {
+  if (h->static_kind == 1) return launch_mppi_t<Ref4Table>(h, a, r);
+  if (h->static_kind == 2) return launch_mppi_t<Dh7Table>(h, a, r);
+  MT_DISPATCH_D(h->D, launch_mppi_d, h, a, r);
+}
 // sample_plans_kernel: a thread per (env, step, candidate); it needs the number of joints only
 template <int D>
 void launch_sample_plans_d(mt_handle h, const CemArgs& r, float* plans, int64_t ld, int64_t cand_stride) {
@@ -1246,6 +1262,9 @@ const char* mt_describe_dispatch(mt_handle h) {
       // mt_cem: shoot's shape, the candidates drawn in the kernel
       ",\"cem\":{\"usable\":" + b(fusable(h)) + ",\"envs_per_block\":" + num(kShootEnvs) + ",\"waves_per_block\":" + num(kShootWaves) +
       ",\"max_candidates\":64}" +
+      // mt_mppi: cem's shape, every candidate weighted by a power of decay
+      ",\"mppi\":{\"usable\":" + b(fusable(h)) + ",\"envs_per_block\":" + num(kShootEnvs) + ",\"waves_per_block\":" + num(kShootWaves) +
+      ",\"max_candidates\":64,\"max_steps\":" + num(kMppiMaxSteps) + "}" +
       ",\"reset\":{\"lanes_per_env\":" + num(h->reset_split ? 4 : 1) + "}" +
       // the ground test's interior poses on dense lanes of the block: the step launches that take it (the single-env view,
       // the rollout, tape and shoot kernels never do)
@@ -2254,6 +2273,121 @@ int mt_cem(mt_handle h, const struct mt_cem* s) {
   e.inv_e = 1.0f / (float)s->n_elites;  // the fp32 nearest to 1 / E
   launch_cem(h, h->args, e);            // reads the state, writes the caller's rows only
   rc = check_launch(h, "cem_kernel");
+  if (rc || H == 0) return rc;
+  // the commit: mt_rollout_tape(n_steps = H, actions = chosen_out), host bookkeeping included
+  if (auto_reset) {
+    h->args.seed_lo = (uint32_t)s->seed;
+    h->args.seed_hi = (uint32_t)(s->seed >> 32);
+    int rcg = order_behind_inplace_gather(h, h->stream);  // the in-kernel re-arm writes MT_F_LAST_RETURN
+    if (rcg) return rcg;
+  }
+  TapeArgs r{};
+  r.tape = s->chosen_out;
+  r.tape_ld = s->chosen_ld;
+  r.reward_log = s->reward_log;
+  r.done_log = s->done_log;
+  r.log_ld = s->log_ld;
+  r.return_out = s->return_out;
+  r.T = H;
+  r.auto_reset = auto_reset ? 1u : 0u;
+  r.nt_loads = h->tape_nt_loads ? 1u : 0u;
+  r.seed_lo = (uint32_t)s->seed;
+  r.seed_hi = (uint32_t)(s->seed >> 32);
+  r.radius = h->cfg.radius;
+  launch_tape(h, h->args, r);
+  h->args.flags &= ~kFlagWholeGoals;  // drawn angles are anybody's floats
+  h->codes_valid = false;             // the kernel writes targets as floats only
+  return check_launch(h, "rollout_tape_kernel");
+}
+
+int mt_mppi(mt_handle h, const struct mt_mppi* s) {
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  MT_REQUIRE(h, s != nullptr, "mppi is NULL");
+  MT_REQUIRE(h, s->struct_size == (int32_t)sizeof(struct mt_mppi), "mt_mppi.struct_size does not match this library");
+  MT_REQUIRE(h, s->reserved == 0, "mt_mppi.reserved must be 0");
+  static_assert(MT_MPPI_MAX_STEPS == kMppiMaxSteps, "the header's horizon limit is the kernel's table size");
+  MT_REQUIRE(h, s->n_steps >= 0 && s->n_steps <= MT_MPPI_MAX_STEPS, "mt_mppi.n_steps must be 0..127");
+  MT_REQUIRE(h, s->n_candidates >= 1 && s->n_candidates <= 64, "mt_mppi.n_candidates must be 1..64");
+  MT_REQUIRE(h, (s->flags & ~(MT_MPPI_AUTO_RESET | MT_MPPI_KEEP_MEAN)) == 0, "mt_mppi.flags: unknown MT_MPPI_* flag");
+  // (bit patterns: the build is -ffinite-math-only; 0x47000000 = 32768.0f, the largest angle a step accepts)
+  MT_REQUIRE(h, first_unusable(&s->lo, 1, 0x47000000u) < 0 && first_unusable(&s->hi, 1, 0x47000000u) < 0,
+             "mt_mppi.lo / hi must be finite and within +-32768 degrees");
+  MT_REQUIRE(h, s->lo <= s->hi, "mt_mppi.lo must be <= hi");
+  const bool auto_reset = (s->flags & MT_MPPI_AUTO_RESET) != 0;
+  const int T = s->n_steps, H = s->commit_steps;
+  MT_REQUIRE(h, H >= 0 && H <= T, "mt_mppi.commit_steps must be 0..n_steps");
+  MT_REQUIRE(h, !(auto_reset && H == 0), "MT_MPPI_AUTO_RESET with mt_mppi.commit_steps == 0: an evaluation re-arms nothing");
+  MT_REQUIRE(h, first_unusable(&s->sigma_min, 1, kMaxFiniteBits) < 0 && s->sigma_min >= 0.f, "mt_mppi.sigma_min must be finite and >= 0");
+  // 0x3F800000 = 1.0f: a NaN, an inf or anything beyond 1 fails the first test, a negative value (not -0) the second
+  MT_REQUIRE(h, first_unusable(&s->decay, 1, 0x3F800000u) < 0 && s->decay >= 0.f, "mt_mppi.decay must be finite and within 0..1");
+  if (!fusable(h)) {  // the rollout kernels do not implement these
+    const char* what = h->custom_frames ? "custom obs_frame / ee_frame"
+                       : h->trace       ? "MT_FLAG_TRACE"
+                       : h->lds_table   ? "MT_FLAG_DH_IN_LDS"
+                       : h->trig == 2   ? "MT_FLAG_HW_TRIG"
+                       : (h->cfg.flags & MT_FLAG_DIRECT_TRIG) ? "MT_FLAG_DIRECT_TRIG"
+                       : h->trig == 1   ? "substeps beyond the recurrence's reach (per-pose trigonometry)"
+                                        : "a profiling flag (MT_FLAG_ABLATE_*)";
+    return fail(h, MT_ERR_UNSUPPORTED, std::string("mt_mppi: not available on a handle with ") + what);
+  }
+  if (!h->is_reset) return fail(h, MT_ERR_STATE, "mt_mppi before mt_reset / mt_reset_random");
+  if (T == 0) return MT_OK;
+  const int64_t n = h->n, rows = (int64_t)T * h->D;
+  MT_REQUIRE(h, s->mean != nullptr && s->sigma != nullptr, "mt_mppi.mean / sigma is NULL");
+  MT_REQUIRE(h, s->ld >= n, "mt_mppi.ld is smaller than n_envs");
+  MT_REQUIRE(h, !(s->sigma_out && !s->mean_out), "mt_mppi.sigma_out without mean_out");
+  MT_REQUIRE(h, !s->mean_out || s->out_ld >= n, "mt_mppi.out_ld is smaller than n_envs");
+  MT_REQUIRE(h, !s->returns_out || s->ret_ld >= n, "mt_mppi.ret_ld is smaller than n_envs");
+  MT_REQUIRE(h, !s->weights_out || s->w_ld >= n, "mt_mppi.w_ld is smaller than n_envs");
+  MT_REQUIRE(h, !(H > 0 && s->chosen_out == nullptr), "mt_mppi.chosen_out is NULL with commit_steps > 0");
+  MT_REQUIRE(h, !(H > 0) || s->chosen_ld >= n, "mt_mppi.chosen_ld is smaller than n_envs");
+  MT_REQUIRE(h, !(H > 0 && (s->reward_log || s->done_log)) || s->log_ld >= n, "mt_mppi.log_ld is smaller than n_envs");
+  // mt_cem's in-place rule: an output EXACTLY on its input (same base, same pitch) is read and written by one thread per
+  // element; any other overlap would let one block read another's writes
+  const bool same_m = s->mean_out == s->mean && s->out_ld == s->ld, same_s = s->sigma_out == s->sigma && s->out_ld == s->ld;
+  MT_REQUIRE(h, same_m || !rows_overlap(s->mean_out, rows, s->out_ld, s->mean, rows, s->ld, n), "mt_mppi.mean_out overlaps mean without being mean");
+  MT_REQUIRE(h, same_s || !rows_overlap(s->sigma_out, rows, s->out_ld, s->sigma, rows, s->ld, n), "mt_mppi.sigma_out overlaps sigma without being sigma");
+  MT_REQUIRE(h, !rows_overlap(s->mean_out, rows, s->out_ld, s->sigma, rows, s->ld, n), "mt_mppi.mean_out overlaps sigma");
+  MT_REQUIRE(h, !rows_overlap(s->sigma_out, rows, s->out_ld, s->mean, rows, s->ld, n), "mt_mppi.sigma_out overlaps mean");
+  MT_REQUIRE(h, !rows_overlap(s->mean_out, rows, s->out_ld, s->sigma_out, rows, s->out_ld, n), "mt_mppi.mean_out overlaps sigma_out");
+  if (H > 0) {
+    const int64_t hr = (int64_t)H * h->D;
+    MT_REQUIRE(h, !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->mean, rows, s->ld, n) &&
+                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->sigma, rows, s->ld, n) &&
+                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->mean_out, rows, s->out_ld, n) &&
+                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->sigma_out, rows, s->out_ld, n),
+               "mt_mppi.chosen_out overlaps mean / sigma / mean_out / sigma_out");
+  }
+  MT_ENTER(h);
+  MppiArgs e{};
+  e.mean = s->mean;
+  e.sigma = s->sigma;
+  e.ld = s->ld;
+  e.mean_out = s->mean_out;
+  e.sigma_out = s->sigma_out;
+  e.out_ld = s->out_ld;
+  e.returns_out = s->returns_out;
+  e.ret_ld = s->ret_ld;
+  e.weights_out = s->weights_out;
+  e.w_ld = s->w_ld;
+  e.weight_sum_out = s->weight_sum_out;
+  e.best_out = s->best_out;
+  e.best_return_out = s->best_return_out;
+  e.chosen_out = H > 0 ? s->chosen_out : nullptr;
+  e.chosen_ld = s->chosen_ld;
+  e.T = T;
+  e.C = s->n_candidates;
+  e.H = H;
+  e.draw = s->draw;
+  e.keep_mean = (s->flags & MT_MPPI_KEEP_MEAN) ? 1u : 0u;
+  e.seed_lo = (uint32_t)s->seed;
+  e.seed_hi = (uint32_t)(s->seed >> 32);
+  e.lo = s->lo;
+  e.hi = s->hi;
+  e.sigma_min = s->sigma_min;
+  e.decay = s->decay;
+  launch_mppi(h, h->args, e);  // reads the state, writes the caller's rows only
+  int rc = check_launch(h, "mppi_kernel");
   if (rc || H == 0) return rc;
   // the commit: mt_rollout_tape(n_steps = H, actions = chosen_out), host bookkeeping included
   if (auto_reset) {

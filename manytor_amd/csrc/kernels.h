@@ -2667,8 +2667,8 @@ struct CemArgs {
 };
 
 // the D angles of candidate c at step t from the env's mean / sigma rows of that step
-template <int D>
-__device__ __forceinline__ void plan_angles(const CemArgs& r, uint64_t seed, uint64_t env_id, uint32_t c, uint32_t t,
+template <int D, class Args>
+__device__ __forceinline__ void plan_angles(const Args& r, uint64_t seed, uint64_t env_id, uint32_t c, uint32_t t,
                                             const float (&mu)[D], const float (&sg)[D], float (&x)[D]) {
   static_assert(D <= 8, "a plan step is at most two Philox blocks");
   const bool zero = (r.keep_mean != 0u) & (c == 0u);
@@ -2854,6 +2854,225 @@ __global__ __launch_bounds__(kBlock) void cem_kernel(const StepArgs a, const Cem
     for (int j = 0; j < D; ++j) {
       str(r.mean_out + ((int64_t)s * D + j) * r.out_ld, o4, m[j]);
       str(r.sigma_out + ((int64_t)s * D + j) * r.out_ld, o4, fmaxf(sqrtf(v[j] * r.inv_e), r.sigma_min));
+    }
+  }
+}
+
+// The return of drawn candidate c over r.T steps from the start pose g0 and alive mask am0: cem_kernel's scoring loop,
+// statement for statement, as a function (Args: any block with mean / sigma / ld / T and plan_angles' fields).  cem_kernel
+// itself keeps the loop written out: routed through this function it compiles to one VGPR more in every instantiation
+// (the callee is simplified on its own before it is inlined), and its register rows are pinned.
+template <class Tbl, class Args>
+__device__ __forceinline__ float plan_return(const Tbl& t, const StepArgs& a, const Args& r, uint64_t seed, uint64_t env_id, uint32_t c,
+                                             LaneOffset<true> o4, const float (&g0)[Tbl::D], uint32_t am0, const float* col) {
+  constexpr int D = Tbl::D;
+  float g[D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) g[j] = g0[j];
+  uint32_t am = am0;
+  float ret = 0.f;
+  PoseCache<D> pose;
+  bool pose_valid = false;
+  for (int s = 0; s < r.T; ++s) {
+    float act[D], raw[D], mu[D], sg[D], el[3], e[3];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {  // requested at the head of the step: the Philox rounds below cover the latency
+      mu[j] = tape_load(r.mean + ((int64_t)s * D + j) * r.ld, o4, false);
+      sg[j] = tape_load(r.sigma + ((int64_t)s * D + j) * r.ld, o4, false);
+    }
+    plan_angles<D>(r, seed, env_id, c, (uint32_t)s, mu, sg, raw);
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < D; ++j) bad |= unusable_angle(raw[j]);
+#pragma unroll
+    for (int j = 0; j < D; ++j) act[j] = bad ? g[j] : raw[j];  // the env holds its pose this step
+
+    const float zmin = route_kinematics<Tbl, 0, true, false>(t, a.S, a.inv_sm1, g, act, el, e, &pose, pose_valid, nullptr, false);
+    pose_valid = true;
+    const bool ground = zmin < 0.f;
+    uint32_t nam = am;
+    for (int k = 0; k < a.K; ++k) {
+      if (!((am >> k) & 1u)) continue;
+      const float* pk = col + 3 * k * kShootEnvs;
+      if (within_box(e, pk[0], pk[kShootEnvs], pk[2 * kShootEnvs], a.tol)) nam &= ~(1u << k);
+    }
+    ret += (float)(ground ? -1 : ((nam != am) ? 1 : 0));
+    am = nam;
+#pragma unroll
+    for (int j = 0; j < D; ++j) g[j] = act[j];
+  }
+  return ret;
+}
+
+// ---------------------------------------------------------------------------
+// mt_mppi: one MPPI (model-predictive path integral) iteration where the data sits.  cem_kernel's shape and scoring --
+// the same plan stream, the same block / wave / lane layout, plan_return -- so the evaluation equals shoot_kernel on the
+// block mt_sample_plans writes, bit for bit.  There is no elite set: candidate c weighs rho^k, k = best return - its own.
+//   weights  : a step's reward is -1, 0 or +1, so a return is an integer in [-T, T] and the gap k an integer in [0, 2T].
+//              W[0] = 1, W[k] = W[k-1] * rho (one rounding each) is built by thread 0 in LDS ahead of the first barrier;
+//              no transcendental function is evaluated and numpy restates the table bit for bit.
+//   select   : behind the scoring barrier every lane reads its own column of the [C][64] score tile (conflict-free) for
+//              the maximum and the lowest index that reaches it.  Behind a third barrier each wave turns ITS rows of the
+//              tile into weights (w = W[(int)(top - score)]) and writes them to weights_out.
+//   refit    : behind the fourth barrier every lane sums its column, S = sum of w_c from +0 in ascending c, and the waves
+//              split the T steps.  For step t a lane walks c = 0 .. C-1, regenerates the angles (nothing is stored) and
+//              accumulates A += w_c * x_c; m = A / S is one correctly rounded division.  With sigma_out a second walk
+//              accumulates Q += w_c * (x_c - m)^2 and sigma_out = max(sqrt(Q / S), sigma_min).  A candidate whose weight
+//              is 0 in every lane of the wave is skipped: its terms are +-0 on sums that started from +0.  With mean_out
+//              == mean the element is read and written by this one thread, after the block's last scoring read.  The same
+//              pass writes rows t < H of chosen_out from the best candidate.
+// No atomics on global memory, no init pass, no dependence between blocks.  Tail lanes meet every barrier and store nothing.
+// ---------------------------------------------------------------------------
+constexpr int kMppiMaxSteps = 127;
+constexpr int kMppiTable = 2 * kMppiMaxSteps + 2;  // 2T + 1 <= 255 entries, rounded up to whole 16-byte slots
+struct MppiArgs {
+  const float *mean, *sigma;  // [T * D][ld]
+  int64_t ld;
+  float *mean_out, *sigma_out;  // [T * D][out_ld]; mean_out alone, both, or neither
+  int64_t out_ld;
+  float* returns_out;  // [C][ret_ld] or NULL
+  int64_t ret_ld;
+  float* weights_out;  // [C][w_ld] or NULL
+  int64_t w_ld;
+  float* weight_sum_out;   // [n] or NULL
+  int32_t* best_out;       // [n] or NULL
+  float* best_return_out;  // [n] or NULL
+  float* chosen_out;       // [H * D][chosen_ld] or NULL (H == 0)
+  int64_t chosen_ld;
+  int32_t T, C, H;
+  uint32_t draw, keep_mean;
+  uint32_t seed_lo, seed_hi;
+  float lo, hi, sigma_min, decay;
+};
+
+template <class Tbl>
+__global__ __launch_bounds__(kBlock) void mppi_kernel(const StepArgs a, const MppiArgs r) {
+  // [3K][64] targets, [C][64] returns (then weights), [kMppiTable] powers of decay
+  extern __shared__ __attribute__((aligned(16))) float tile[];
+  constexpr int D = Tbl::D;
+  const Tbl t = TableMaker<Tbl>::make(a.dh);
+  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+  const uint32_t i = blockIdx.x * kShootEnvs + lane;
+  const bool live = i < a.n;
+  LaneOffset<true> o4{i * 4u};
+  const int64_t ld = a.ld;
+  const float* col = tile + lane;
+  float* rets = tile + 3 * a.K * kShootEnvs;
+  float* table = rets + r.C * kShootEnvs;
+  const uint64_t seed = ((uint64_t)r.seed_hi << 32) | r.seed_lo;
+  const uint64_t env_id = (uint64_t)(a.env_base + i);
+
+  float g0[D];
+  uint32_t am0 = 0u;
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) g0[j] = ldr(a.goals + j * ld, o4);
+    am0 = ldr(a.alive, o4);
+    for (int k = (int)w; k < 3 * a.K; k += kShootWaves) tile[k * kShootEnvs + lane] = ldr(a.points + (int64_t)k * ld, o4);
+  }
+  if (threadIdx.x == 0) {  // the recurrence, nothing else: every weight of the call is one of these 2T + 1 floats
+    float p = 1.f;
+    table[0] = p;
+    for (int k = 1; k <= 2 * r.T; ++k) {
+      p = p * r.decay;
+      table[k] = p;
+    }
+  }
+  __syncthreads();
+
+  // ---- score: cem_kernel's loop ----
+  if (live) {
+    for (int c = (int)w; c < r.C; c += kShootWaves) {  // (wave-uniform)
+      const float ret = plan_return<Tbl>(t, a, r, seed, env_id, (uint32_t)c, o4, g0, am0, col);
+      if (r.returns_out) str_stream(r.returns_out + (int64_t)c * r.ret_ld, o4, ret);
+      rets[c * kShootEnvs + lane] = ret;
+    }
+  }
+  __syncthreads();
+
+  // ---- the maximum and the lowest index that reaches it: every wave for itself, a lane reads its own column ----
+  float top = 0.f;
+  int32_t top_c = 0;
+  if (live) {
+    top = rets[lane];  // (C >= 1)
+    for (int c = 1; c < r.C; ++c) {
+      const float v = rets[c * kShootEnvs + lane];
+      if (v > top) {  // ascending c: a tie keeps the earlier candidate
+        top = v;
+        top_c = c;
+      }
+    }
+  }
+  __syncthreads();  // every wave has read the scores it needs
+
+  // ---- scores -> weights: each wave its own rows ----
+  if (live) {
+    for (int c = (int)w; c < r.C; c += kShootWaves) {
+      const int gap = (int)(top - rets[c * kShootEnvs + lane]);  // exact: both are integers within +-T
+      const float wt = table[gap];
+      rets[c * kShootEnvs + lane] = wt;
+      if (r.weights_out) str_stream(r.weights_out + (int64_t)c * r.w_ld, o4, wt);
+    }
+  }
+  __syncthreads();
+  if (!live) return;  // (no barrier below)
+
+  float sum = 0.f;
+  for (int c = 0; c < r.C; ++c) sum += rets[c * kShootEnvs + lane];
+  if (w == 0) {
+    if (r.best_out) str(r.best_out, o4, top_c);
+    if (r.best_return_out) str_stream(r.best_return_out, o4, top);
+    if (r.weight_sum_out) str_stream(r.weight_sum_out, o4, sum);
+  }
+
+  // ---- refit and the chosen rows: the waves split the steps ----
+  const bool refit = r.mean_out != nullptr, spread = r.sigma_out != nullptr;
+  for (int s = (int)w; s < r.T; s += kShootWaves) {  // (wave-uniform)
+    const bool pick = s < r.H;
+    if (!refit && !pick) break;  // (H <= T and s ascends: nothing further down either)
+    float mu[D], sg[D], x[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      mu[j] = tape_load(r.mean + ((int64_t)s * D + j) * r.ld, o4, false);
+      sg[j] = tape_load(r.sigma + ((int64_t)s * D + j) * r.ld, o4, false);
+    }
+    if (pick) {
+      plan_angles<D>(r, seed, env_id, (uint32_t)top_c, (uint32_t)s, mu, sg, x);
+#pragma unroll
+      for (int j = 0; j < D; ++j) str(r.chosen_out + ((int64_t)s * D + j) * r.chosen_ld, o4, x[j]);
+    }
+    if (!refit) continue;
+    float m[D] = {}, q[D] = {};
+    for (int c = 0; c < r.C; ++c) {
+      const float wt = rets[c * kShootEnvs + lane];
+      if (!__any(wt != 0.f)) continue;  // (wave-uniform)
+      plan_angles<D>(r, seed, env_id, (uint32_t)c, (uint32_t)s, mu, sg, x);
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        const float wx = wt * x[j];
+        m[j] = m[j] + wx;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < D; ++j) m[j] = m[j] / sum;
+    if (spread) {
+      for (int c = 0; c < r.C; ++c) {
+        const float wt = rets[c * kShootEnvs + lane];
+        if (!__any(wt != 0.f)) continue;
+        plan_angles<D>(r, seed, env_id, (uint32_t)c, (uint32_t)s, mu, sg, x);
+#pragma unroll
+        for (int j = 0; j < D; ++j) {
+          const float d = x[j] - m[j];
+          const float dd = d * d;
+          const float wd = wt * dd;
+          q[j] = q[j] + wd;
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      str(r.mean_out + ((int64_t)s * D + j) * r.out_ld, o4, m[j]);
+      if (spread) str(r.sigma_out + ((int64_t)s * D + j) * r.out_ld, o4, fmaxf(sqrtf(q[j] / sum), r.sigma_min));
     }
   }
 }

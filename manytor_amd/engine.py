@@ -635,6 +635,108 @@ class StepEngine:
             self.version += 1
         return out
 
+    def mppi(self, mean, sigma, *, candidates, temperature=None, decay=None, draw=0, seed=0x5EED, commit=0, auto_reset=False,
+             lo=-180., hi=180., sigma_min=0., keep_mean=False, fit_sigma=False, inplace=False, all_returns=False,
+             weights=False, log=False, returns=False):
+        """One MPPI iteration in one call (mt_mppi): C = `candidates` plans per env are DRAWN in the kernel around `mean` /
+        `sigma` exactly as cem() draws them (the block is what sample_plans() returns for the same arguments, but it never
+        exists) and scored exactly as shoot() scores them; candidate c then weighs decay ** (best_return - its return) --
+        give exactly one of `temperature` (lambda > 0: decay = float32(exp(-1 / lambda))) and `decay` (0 <= decay <= 1; 0
+        is the hard maximum, 1 the plain average) -- and `mean` becomes the weighted mean of all candidates, with
+        fit_sigma=True `sigma` their weighted standard deviation, floored at sigma_min.  Returns a dict of device tensors:
+        `best` (N,) int32, `best_return` (N,) float32, `weight_sum` (N,) float32, `mean` (T, D, N) -- a new tensor, or with
+        inplace=True the argument itself, overwritten -- and with fit_sigma `sigma` likewise; `candidate_returns` (C, N)
+        with all_returns=True, `weights` (C, N) with weights=True.  commit=H > 0 also executes steps 0..H-1 of each env's
+        best plan for real, as rollout_actions(chosen, layout="soa", auto_reset=, seed=) would: `chosen` (H, D, N) holds
+        those angles, log=True adds `reward` / `done` (H, N) and returns=True `returns` (N,).  At most 127 steps.  Stream
+        rules as cem(); with commit == 0 nothing resident changes."""
+        import torch
+        commit = int(commit)
+        if auto_reset and commit == 0:
+            raise ValueError("auto_reset needs commit > 0: an evaluation re-arms nothing")
+        c, lo, hi = self._cem_scalars(candidates, lo, hi)
+        if (temperature is None) == (decay is None):
+            raise ValueError("give exactly one of temperature and decay")
+        if temperature is not None:
+            lam = float(temperature)
+            if not (np.isfinite(lam) and lam > 0.0):
+                raise ValueError(f"temperature must be finite and > 0, got {lam}")
+            rho = float(np.float32(np.exp(-1.0 / lam)))
+        else:
+            rho = float(decay)
+            if not (np.isfinite(rho) and 0.0 <= rho <= 1.0):
+                raise ValueError(f"decay must be finite and within 0..1, got {rho}")
+            rho = float(np.float32(rho))
+        sigma_min = float(sigma_min)
+        if not (np.isfinite(sigma_min) and sigma_min >= 0.0):
+            raise ValueError(f"sigma_min must be finite and >= 0, got {sigma_min}")
+        steps = getattr(mean, "shape", None)                     # (ahead of the tensor checks: the horizon is the call's own limit)
+        if steps is not None and len(steps) == 3 and int(steps[0]) > L.MPPI_MAX_STEPS:
+            raise ValueError(f"at most {L.MPPI_MAX_STEPS} steps, got {int(steps[0])}")
+        mean, sigma, T, ld = self._cem_rows(mean, sigma)
+        if not 0 <= commit <= T:
+            raise ValueError(f"commit must be 0..T = {T}, got {commit}")
+        n, d = self.n_envs, self.dof
+        dev = mean.device
+        alloc = torch.empty if T else torch.zeros                # (T == 0: the call is a no-op and writes nothing)
+        out = {"best": alloc(n, dtype=torch.int32, device=dev), "best_return": alloc(n, dtype=torch.float32, device=dev),
+               "weight_sum": alloc(n, dtype=torch.float32, device=dev)}
+        if inplace:
+            out["mean"], out_ld = mean, ld
+            if fit_sigma:
+                out["sigma"] = sigma
+        else:
+            out["mean"], out_ld = torch.empty((T, d, n), dtype=torch.float32, device=dev), n
+            if fit_sigma:
+                out["sigma"] = torch.empty((T, d, n), dtype=torch.float32, device=dev)
+        if all_returns:
+            out["candidate_returns"] = alloc((c, n), dtype=torch.float32, device=dev)
+        if weights:
+            out["weights"] = alloc((c, n), dtype=torch.float32, device=dev)
+        if commit:
+            out["chosen"] = torch.empty((commit, d, n), dtype=torch.float32, device=dev)
+        if log:
+            out["reward"] = torch.empty((commit, n), dtype=torch.int8, device=dev)
+            out["done"] = torch.empty((commit, n), dtype=torch.uint8, device=dev)
+        if returns:
+            out["returns"] = (alloc if commit else torch.zeros)(n, dtype=torch.float32, device=dev)
+        arg = L.MtMppi()
+        arg.struct_size = C.sizeof(L.MtMppi)
+        arg.n_steps, arg.n_candidates, arg.commit_steps = T, c, commit
+        arg.draw = int(draw) & 0xFFFFFFFF
+        arg.decay = rho
+        arg.mean, arg.sigma, arg.ld = (mean.data_ptr(), sigma.data_ptr(), ld) if T else (None, None, n)
+        arg.mean_out = out["mean"].data_ptr() if T else None
+        arg.sigma_out = out["sigma"].data_ptr() if T and fit_sigma else None
+        arg.out_ld = out_ld
+        arg.lo, arg.hi, arg.sigma_min = lo, hi, sigma_min
+        arg.returns_out = out["candidate_returns"].data_ptr() if all_returns else None
+        arg.ret_ld = n
+        arg.weights_out = out["weights"].data_ptr() if weights else None
+        arg.w_ld = n
+        arg.weight_sum_out = out["weight_sum"].data_ptr()
+        arg.best_out = out["best"].data_ptr()
+        arg.best_return_out = out["best_return"].data_ptr()
+        arg.chosen_out = out["chosen"].data_ptr() if commit else None
+        arg.chosen_ld = n
+        arg.reward_log = out["reward"].data_ptr() if log and commit else None
+        arg.done_log = out["done"].data_ptr() if log and commit else None
+        arg.log_ld = n
+        arg.return_out = out["returns"].data_ptr() if returns and commit else None
+        arg.seed = int(seed)
+        arg.flags = (L.MPPI_AUTO_RESET if auto_reset else 0) | (L.MPPI_KEEP_MEAN if keep_mean else 0)
+        arg.reserved = 0
+        cur = int(torch.cuda.current_stream(self.device).cuda_stream)
+        ordered = getattr(self, "_caller_stream", None) == cur   # the engine launches on torch's current stream
+        if not ordered:
+            torch.cuda.current_stream(self.device).synchronize()
+        self._call(self._lib.mt_mppi, C.byref(arg))
+        if not ordered:
+            self.sync()     # mean, sigma and the outputs are torch's memory: done with before torch may reuse or read it
+        if commit and T:
+            self.version += 1
+        return out
+
     def observe(self):
         """Environment.get_observations (manytor.py:141-153); result in field OBS."""
         self._call(self._lib.mt_observe)
