@@ -802,6 +802,27 @@ void launch_tape(mt_handle h, const StepArgs& a, const TapeArgs& r) {
   MT_DISPATCH_D(h->D, launch_tape_d, h, a, r);
 }
 
+// f(TableTag<Tbl>{}) with the handle's table type: the kernels of the planner calls have no other compile-time axis.
+template <class Tbl>
+struct TableTag {
+  using type = Tbl;
+};
+template <class F>
+void with_table(const mt_engine* h, F&& f) {
+  if (h->static_kind == 1) return f(TableTag<Ref4Table>{});
+  if (h->static_kind == 2) return f(TableTag<Dh7Table>{});
+  switch (h->D) {
+    case 2: return f(TableTag<RtTable<2>>{});
+    case 3: return f(TableTag<RtTable<3>>{});
+    case 4: return f(TableTag<RtTable<4>>{});
+    case 5: return f(TableTag<RtTable<5>>{});
+    case 6: return f(TableTag<RtTable<6>>{});
+    case 7: return f(TableTag<RtTable<7>>{});
+    case 8: return f(TableTag<RtTable<8>>{});
+    default: return;
+  }
+}
+
 // mt_shoot's commit: rollout_tape_kernel with every env following the plane its evaluation chose (SELECT).  One form, no
 // next-step prefetch (it was measured for the plain tape only).
 template <class Tbl>
@@ -812,14 +833,8 @@ void launch_tape_select_t(mt_handle h, const StepArgs& a, const TapeArgs& r) {
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL((rollout_tape_kernel<Tbl, false, true>), grid_for(a.n), dim3(kBlock), lds, h->stream, a, r);
 }
-template <int D>
-void launch_tape_select_d(mt_handle h, const StepArgs& a, const TapeArgs& r) {
-  launch_tape_select_t<RtTable<D>>(h, a, r);
-}
 void launch_tape_select(mt_handle h, const StepArgs& a, const TapeArgs& r) {
-  if (h->static_kind == 1) return launch_tape_select_t<Ref4Table>(h, a, r);
-  if (h->static_kind == 2) return launch_tape_select_t<Dh7Table>(h, a, r);
-  MT_DISPATCH_D(h->D, launch_tape_select_d, h, a, r);
+  with_table(h, [&](auto tag) { launch_tape_select_t<typename decltype(tag)::type>(h, a, r); });
 }
 
 // shoot_kernel on the whole batch: a block per 64 envs, its four waves share the candidates (kernels.h).
@@ -829,14 +844,8 @@ void launch_shoot_t(mt_handle h, const StepArgs& a, const ShootArgs& r) {
   const size_t lds = ((size_t)3 * h->K + 2 * kShootWaves) * kShootEnvs * sizeof(float);
   hipLaunchKernelGGL((shoot_kernel<Tbl>), dim3((unsigned)((a.n + kShootEnvs - 1) / kShootEnvs)), dim3(kBlock), lds, h->stream, a, r);
 }
-template <int D>
-void launch_shoot_d(mt_handle h, const StepArgs& a, const ShootArgs& r) {
-  launch_shoot_t<RtTable<D>>(h, a, r);
-}
 void launch_shoot(mt_handle h, const StepArgs& a, const ShootArgs& r) {
-  if (h->static_kind == 1) return launch_shoot_t<Ref4Table>(h, a, r);
-  if (h->static_kind == 2) return launch_shoot_t<Dh7Table>(h, a, r);
-  MT_DISPATCH_D(h->D, launch_shoot_d, h, a, r);
+  with_table(h, [&](auto tag) { launch_shoot_t<typename decltype(tag)::type>(h, a, r); });
 }
 
 // cem_kernel on the whole batch: shoot_kernel's shape plus the [C][64] score tile, the four waves' elite masks and the
@@ -846,15 +855,10 @@ void launch_cem_t(mt_handle h, const StepArgs& a, const CemArgs& r) {
   const size_t lds = ((size_t)3 * h->K + (size_t)r.C + 2 * kShootWaves + 1) * kShootEnvs * sizeof(float);
   hipLaunchKernelGGL((cem_kernel<Tbl>), dim3((unsigned)((a.n + kShootEnvs - 1) / kShootEnvs)), dim3(kBlock), lds, h->stream, a, r);
 }
-template <int D>
-void launch_cem_d(mt_handle h, const StepArgs& a, const CemArgs& r) {
-  launch_cem_t<RtTable<D>>(h, a, r);
-}
 void launch_cem(mt_handle h, const StepArgs& a, const CemArgs& r) {
-  if (h->static_kind == 1) return launch_cem_t<Ref4Table>(h, a, r);
-  if (h->static_kind == 2) return launch_cem_t<Dh7Table>(h, a, r);
-  MT_DISPATCH_D(h->D, launch_cem_d, h, a, r);
+  with_table(h, [&](auto tag) { launch_cem_t<typename decltype(tag)::type>(h, a, r); });
 }
+
 // mppi_kernel on the whole batch: cem_kernel's shape; LDS holds the target tile, the [C][64] score / weight tile and the
 // table of 2T + 1 <= 255 powers of decay (at most 41 KB: K = 32, C = 64).
 template <class Tbl>
@@ -862,15 +866,10 @@ void launch_mppi_t(mt_handle h, const StepArgs& a, const MppiArgs& r) {
   const size_t lds = (((size_t)3 * h->K + (size_t)r.C) * kShootEnvs + kMppiTable) * sizeof(float);
   hipLaunchKernelGGL((mppi_kernel<Tbl>), dim3((unsigned)((a.n + kShootEnvs - 1) / kShootEnvs)), dim3(kBlock), lds, h->stream, a, r);
 }
-template <int D>
-void launch_mppi_d(mt_handle h, const StepArgs& a, const MppiArgs& r) {
-  launch_mppi_t<RtTable<D>>(h, a, r);
-}
 void launch_mppi(mt_handle h, const StepArgs& a, const MppiArgs& r) {
-  if (h->static_kind == 1) return launch_mppi_t<Ref4Table>(h, a, r);
-  if (h->static_kind == 2) return launch_mppi_t<Dh7Table>(h, a, r);
-  MT_DISPATCH_D(h->D, launch_mppi_d, h, a, r);
+  with_table(h, [&](auto tag) { launch_mppi_t<typename decltype(tag)::type>(h, a, r); });
 }
+
 // sample_plans_kernel: a thread per (env, step, candidate); it needs the number of joints only
 template <int D>
 void launch_sample_plans_d(mt_handle h, const CemArgs& r, float* plans, int64_t ld, int64_t cand_stride) {
@@ -880,6 +879,20 @@ void launch_sample_plans_d(mt_handle h, const CemArgs& r, float* plans, int64_t 
 
 // The rollout kernels implement the default trigonometry and the reference's frame rows only.
 bool fusable(mt_handle h) { return h->trig == 0 && !h->lds_table && !h->trace && !h->custom_frames; }
+// Which of these a handle that is not fusable has: the first that applies.
+const char* unfusable_reason(const mt_engine* h) {
+  return h->custom_frames                        ? "custom obs_frame / ee_frame"
+         : h->trace                              ? "MT_FLAG_TRACE"
+         : h->lds_table                          ? "MT_FLAG_DH_IN_LDS"
+         : h->trig == 2                          ? "MT_FLAG_HW_TRIG"
+         : (h->cfg.flags & MT_FLAG_DIRECT_TRIG) ? "MT_FLAG_DIRECT_TRIG"
+         : h->trig == 1                          ? "substeps beyond the recurrence's reach (per-pose trigonometry)"
+                                                 : "a profiling flag (MT_FLAG_ABLATE_*)";
+}
+// The refusal of the calls that exist on the rollout kernels only (mt_rollout_tape and the planners on top of it).
+int fail_unfusable(mt_handle h, const char* who) {
+  return fail(h, MT_ERR_UNSUPPORTED, std::string(who) + ": not available on a handle with " + unfusable_reason(h));
+}
 
 // Does mt_rollout(n_steps >= 2) on this handle run k steps per launch through the rollout kernels right now?
 bool rollout_is_multi_step(mt_handle h) { return h->multi_k > 1 && fusable(h); }
@@ -992,6 +1005,143 @@ static int per_chain(mt_handle h, int chains, const char* what, F&& fn) {
 
 constexpr uint32_t kMaxAngleBits = 0x47000000u;   // 32768.0f: the bound of unusable_angle (kernels.h)
 constexpr uint32_t kMaxFiniteBits = 0x7F7FFFFFu;  // FLT_MAX
+
+// ---- what mt_rollout_tape, mt_shoot, mt_cem and mt_mppi (and mt_sample_plans) share on the host ------------------------
+// The commit they all end in: rollout_tape_kernel on the whole batch and the bookkeeping of a call that moves the state.
+// The caller has set in `r` what is its own: the tape and the logs (tape_args), dry_run, nt_loads and, with `select`
+// (mt_shoot: env i follows the plane r.best[i] of a stack of tapes), best / cand_stride.
+static int commit_tape(mt_handle h, TapeArgs& r, uint64_t seed, bool auto_reset, bool select) {
+  if (auto_reset) {
+    h->args.seed_lo = (uint32_t)seed;  // as mt_reset_done(seed) leaves them
+    h->args.seed_hi = (uint32_t)(seed >> 32);
+    int rcg = order_behind_inplace_gather(h, h->stream);  // the in-kernel re-arm writes MT_F_LAST_RETURN
+    if (rcg) return rcg;
+  }
+  r.auto_reset = auto_reset ? 1u : 0u;
+  r.seed_lo = (uint32_t)seed;
+  r.seed_hi = (uint32_t)(seed >> 32);
+  r.radius = h->cfg.radius;
+  if (select)
+    launch_tape_select(h, h->args, r);
+  else
+    launch_tape(h, h->args, r);
+  if (!r.dry_run) {
+    h->args.flags &= ~kFlagWholeGoals;  // tape angles are anybody's floats
+    h->codes_valid = false;             // the kernel writes targets as floats only
+  }
+  return check_launch(h, select ? "rollout_tape_kernel<SELECT>" : "rollout_tape_kernel");
+}
+// T steps of `tape` with the logs and the return row of `s` (a mt_tape, mt_shoot, mt_cem or mt_mppi: the same names)
+template <class S>
+static TapeArgs tape_args(const S* s, const float* tape, int64_t ld, int T) {
+  TapeArgs r{};
+  r.tape = tape;
+  r.tape_ld = ld;
+  r.reward_log = s->reward_log;
+  r.done_log = s->done_log;
+  r.log_ld = s->log_ld;
+  r.return_out = s->return_out;
+  r.T = T;
+  return r;
+}
+
+// struct mt_cem and struct mt_mppi name the candidate stream, the refit and the commit alike; what the messages about
+// them differ in: the struct's name, the prefix of its flags, its longest horizon.
+struct PlanNames {
+  const char *name, *flags;
+  int max_steps;
+};
+constexpr PlanNames kCemNames{"mt_cem", "MT_CEM", 65535}, kMppiNames{"mt_mppi", "MT_MPPI", MT_MPPI_MAX_STEPS};
+static_assert(MT_MPPI_AUTO_RESET == MT_CEM_AUTO_RESET && MT_MPPI_KEEP_MEAN == MT_CEM_KEEP_MEAN, "one set of flag bits");
+static_assert(MT_MPPI_MAX_STEPS == kMppiMaxSteps, "the header's horizon limit is the kernel's table size");
+
+// The candidate stream's parameters, checked and copied into the kernel's block; `who` goes ahead of every message
+// ("mt_sample_plans: ", "mt_cem: ", nothing for mt_mppi).
+template <class S, class Args>
+static int stream_args(mt_handle h, const S* s, const char* who, const PlanNames& p, Args& e) {
+  const std::string w = std::string(who) + p.name;
+  MT_REQUIRE(h, s->n_steps >= 0 && s->n_steps <= p.max_steps, w + ".n_steps must be 0.." + std::to_string(p.max_steps));
+  MT_REQUIRE(h, s->n_candidates >= 1 && s->n_candidates <= 64, w + ".n_candidates must be 1..64");
+  MT_REQUIRE(h, (s->flags & ~(MT_CEM_AUTO_RESET | MT_CEM_KEEP_MEAN)) == 0, w + ".flags: unknown " + p.flags + "_* flag");
+  // (bit patterns: the build is -ffinite-math-only)
+  MT_REQUIRE(h, first_unusable(&s->lo, 1, kMaxAngleBits) < 0 && first_unusable(&s->hi, 1, kMaxAngleBits) < 0,
+             w + ".lo / hi must be finite and within +-32768 degrees");
+  MT_REQUIRE(h, s->lo <= s->hi, w + ".lo must be <= hi");
+  e.mean = s->mean;
+  e.sigma = s->sigma;
+  e.ld = s->ld;
+  e.T = s->n_steps;
+  e.C = s->n_candidates;
+  e.draw = s->draw;
+  e.keep_mean = (s->flags & MT_CEM_KEEP_MEAN) ? 1u : 0u;
+  e.seed_lo = (uint32_t)s->seed;
+  e.seed_hi = (uint32_t)(s->seed >> 32);
+  e.lo = s->lo;
+  e.hi = s->hi;
+  return MT_OK;
+}
+// ... and its rows, which a call with n_steps > 0 needs
+template <class S>
+static int stream_rows(mt_handle h, const S* s, const char* who, const PlanNames& p) {
+  const std::string w = std::string(who) + p.name;
+  MT_REQUIRE(h, s->mean != nullptr && s->sigma != nullptr, w + ".mean / sigma is NULL");
+  MT_REQUIRE(h, s->ld >= h->n, w + ".ld is smaller than n_envs");
+  return MT_OK;
+}
+
+// do [p, p + rows * ld) and [q, q + rows2 * ld2) share a byte?  (rows of n floats, the last one not padded)
+static bool rows_overlap(const float* p, int64_t rows, int64_t ld, const float* q, int64_t rows2, int64_t ld2, int64_t n) {
+  if (!p || !q || rows == 0 || rows2 == 0) return false;
+  const uintptr_t a0 = (uintptr_t)p, a1 = a0 + (uintptr_t)(((rows - 1) * ld + n) * 4);
+  const uintptr_t b0 = (uintptr_t)q, b1 = b0 + (uintptr_t)(((rows2 - 1) * ld2 + n) * 4);
+  return a0 < b1 && b0 < a1;
+}
+static bool weights_fit(const struct mt_cem*, int64_t) { return true; }  // (no such output)
+static bool weights_fit(const struct mt_mppi* s, int64_t n) { return !s->weights_out || s->w_ld >= n; }
+
+// The layout rules of what a refit writes (mean_out / sigma_out, returns_out, chosen_out and the commit's logs; which of
+// mean_out / sigma_out may be NULL is the entry point's own rule, checked ahead of this), then those outputs into the
+// kernel's block.
+template <class S, class Args>
+static int refit_args(mt_handle h, const S* s, const PlanNames& p, Args& e) {
+  const std::string w = std::string(p.name) + ".";
+  const int H = s->commit_steps;
+  const int64_t n = h->n, rows = (int64_t)s->n_steps * h->D;
+  MT_REQUIRE(h, !s->mean_out || s->out_ld >= n, w + "out_ld is smaller than n_envs");
+  MT_REQUIRE(h, !s->returns_out || s->ret_ld >= n, w + "ret_ld is smaller than n_envs");
+  MT_REQUIRE(h, weights_fit(s, n), w + "w_ld is smaller than n_envs");
+  MT_REQUIRE(h, !(H > 0 && s->chosen_out == nullptr), w + "chosen_out is NULL with commit_steps > 0");
+  MT_REQUIRE(h, !(H > 0) || s->chosen_ld >= n, w + "chosen_ld is smaller than n_envs");
+  MT_REQUIRE(h, !(H > 0 && (s->reward_log || s->done_log)) || s->log_ld >= n, w + "log_ld is smaller than n_envs");
+  // the refit may sit EXACTLY on its input (same base, same pitch: every element is then read and written by one thread);
+  // any other overlap of an output with mean / sigma or with the other output would let one block read another's writes
+  const bool same_m = s->mean_out == s->mean && s->out_ld == s->ld, same_s = s->sigma_out == s->sigma && s->out_ld == s->ld;
+  MT_REQUIRE(h, same_m || !rows_overlap(s->mean_out, rows, s->out_ld, s->mean, rows, s->ld, n), w + "mean_out overlaps mean without being mean");
+  MT_REQUIRE(h, same_s || !rows_overlap(s->sigma_out, rows, s->out_ld, s->sigma, rows, s->ld, n), w + "sigma_out overlaps sigma without being sigma");
+  MT_REQUIRE(h, !rows_overlap(s->mean_out, rows, s->out_ld, s->sigma, rows, s->ld, n), w + "mean_out overlaps sigma");
+  MT_REQUIRE(h, !rows_overlap(s->sigma_out, rows, s->out_ld, s->mean, rows, s->ld, n), w + "sigma_out overlaps mean");
+  MT_REQUIRE(h, !rows_overlap(s->mean_out, rows, s->out_ld, s->sigma_out, rows, s->out_ld, n), w + "mean_out overlaps sigma_out");
+  if (H > 0) {
+    const int64_t hr = (int64_t)H * h->D;
+    MT_REQUIRE(h, !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->mean, rows, s->ld, n) &&
+                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->sigma, rows, s->ld, n) &&
+                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->mean_out, rows, s->out_ld, n) &&
+                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->sigma_out, rows, s->out_ld, n),
+               w + "chosen_out overlaps mean / sigma / mean_out / sigma_out");
+  }
+  e.mean_out = s->mean_out;
+  e.sigma_out = s->sigma_out;
+  e.out_ld = s->out_ld;
+  e.returns_out = s->returns_out;
+  e.ret_ld = s->ret_ld;
+  e.best_out = s->best_out;
+  e.best_return_out = s->best_return_out;
+  e.chosen_out = H > 0 ? s->chosen_out : nullptr;
+  e.chosen_ld = s->chosen_ld;
+  e.H = H;
+  e.sigma_min = s->sigma_min;
+  return MT_OK;
+}
 
 extern "C" {
 
@@ -2040,48 +2190,17 @@ int mt_rollout_tape(mt_handle h, const mt_tape* tape) {
   const bool auto_reset = (tape->flags & MT_TAPE_AUTO_RESET) != 0, dry = (tape->flags & MT_TAPE_DRY_RUN) != 0;
   MT_REQUIRE(h, !(auto_reset && dry), "MT_TAPE_DRY_RUN | MT_TAPE_AUTO_RESET: the re-arm writes the return ring");
   MT_REQUIRE(h, tape->n_steps >= 0, "n_steps must be >= 0");
-  if (!fusable(h)) {  // the rollout kernels do not implement these
-    const char* what = h->custom_frames ? "custom obs_frame / ee_frame"
-                       : h->trace       ? "MT_FLAG_TRACE"
-                       : h->lds_table   ? "MT_FLAG_DH_IN_LDS"
-                       : h->trig == 2   ? "MT_FLAG_HW_TRIG"
-                       : (h->cfg.flags & MT_FLAG_DIRECT_TRIG) ? "MT_FLAG_DIRECT_TRIG"
-                       : h->trig == 1   ? "substeps beyond the recurrence's reach (per-pose trigonometry)"
-                                        : "a profiling flag (MT_FLAG_ABLATE_*)";
-    return fail(h, MT_ERR_UNSUPPORTED, std::string("mt_rollout_tape: not available on a handle with ") + what);
-  }
+  if (!fusable(h)) return fail_unfusable(h, "mt_rollout_tape");
   if (!h->is_reset) return fail(h, MT_ERR_STATE, "mt_rollout_tape before mt_reset / mt_reset_random");
   if (tape->n_steps == 0) return MT_OK;
   MT_REQUIRE(h, tape->actions != nullptr, "mt_tape.actions is NULL");
   MT_REQUIRE(h, tape->ld >= h->n, "mt_tape.ld is smaller than n_envs");
   MT_REQUIRE(h, !(tape->reward_log || tape->done_log) || tape->log_ld >= h->n, "mt_tape.log_ld is smaller than n_envs");
   MT_ENTER(h);
-  if (auto_reset) {
-    h->args.seed_lo = (uint32_t)tape->seed;  // as mt_reset_done(seed) leaves them
-    h->args.seed_hi = (uint32_t)(tape->seed >> 32);
-    int rcg = order_behind_inplace_gather(h, h->stream);  // the in-kernel re-arm writes MT_F_LAST_RETURN
-    if (rcg) return rcg;
-  }
-  TapeArgs r{};
-  r.tape = tape->actions;
-  r.tape_ld = tape->ld;
-  r.reward_log = tape->reward_log;
-  r.done_log = tape->done_log;
-  r.log_ld = tape->log_ld;
-  r.return_out = tape->return_out;
-  r.T = tape->n_steps;
-  r.auto_reset = auto_reset ? 1u : 0u;
+  TapeArgs r = tape_args(tape, tape->actions, tape->ld, tape->n_steps);
   r.dry_run = dry ? 1u : 0u;
   r.nt_loads = h->tape_nt_loads ? 1u : 0u;
-  r.seed_lo = (uint32_t)tape->seed;
-  r.seed_hi = (uint32_t)(tape->seed >> 32);
-  r.radius = h->cfg.radius;
-  launch_tape(h, h->args, r);
-  if (!dry) {
-    h->args.flags &= ~kFlagWholeGoals;  // tape angles are anybody's floats
-    h->codes_valid = false;             // the kernel writes targets as floats only
-  }
-  return check_launch(h, "rollout_tape_kernel");
+  return commit_tape(h, r, tape->seed, auto_reset, false);
 }
 
 int mt_shoot(mt_handle h, const struct mt_shoot* s) {
@@ -2095,16 +2214,7 @@ int mt_shoot(mt_handle h, const struct mt_shoot* s) {
   MT_REQUIRE(h, s->n_candidates >= 1 && s->n_candidates <= 64, "mt_shoot.n_candidates must be 1..64");
   MT_REQUIRE(h, s->commit_steps >= 0 && s->commit_steps <= s->n_steps, "mt_shoot.commit_steps must be 0..n_steps");
   MT_REQUIRE(h, !(auto_reset && s->commit_steps == 0), "MT_SHOOT_AUTO_RESET with mt_shoot.commit_steps == 0: an evaluation re-arms nothing");
-  if (!fusable(h)) {  // the rollout kernels do not implement these
-    const char* what = h->custom_frames ? "custom obs_frame / ee_frame"
-                       : h->trace       ? "MT_FLAG_TRACE"
-                       : h->lds_table   ? "MT_FLAG_DH_IN_LDS"
-                       : h->trig == 2   ? "MT_FLAG_HW_TRIG"
-                       : (h->cfg.flags & MT_FLAG_DIRECT_TRIG) ? "MT_FLAG_DIRECT_TRIG"
-                       : h->trig == 1   ? "substeps beyond the recurrence's reach (per-pose trigonometry)"
-                                        : "a profiling flag (MT_FLAG_ABLATE_*)";
-    return fail(h, MT_ERR_UNSUPPORTED, std::string("mt_shoot: not available on a handle with ") + what);
-  }
+  if (!fusable(h)) return fail_unfusable(h, "mt_shoot");
   if (!h->is_reset) return fail(h, MT_ERR_STATE, "mt_shoot before mt_reset / mt_reset_random");
   if (s->n_steps == 0) return MT_OK;
   const int H = s->commit_steps;
@@ -2128,75 +2238,22 @@ int mt_shoot(mt_handle h, const struct mt_shoot* s) {
   launch_shoot(h, h->args, e);  // reads the state, writes the caller's rows only
   int rc = check_launch(h, "shoot_kernel");
   if (rc || H == 0) return rc;
-  // the commit: what mt_rollout_tape(n_steps = H, the gathered tape) does, host bookkeeping included
-  if (auto_reset) {
-    h->args.seed_lo = (uint32_t)s->seed;
-    h->args.seed_hi = (uint32_t)(s->seed >> 32);
-    int rcg = order_behind_inplace_gather(h, h->stream);  // the in-kernel re-arm writes MT_F_LAST_RETURN
-    if (rcg) return rcg;
-  }
-  TapeArgs r{};
-  r.tape = s->actions;
-  r.tape_ld = s->ld;
-  r.reward_log = s->reward_log;
-  r.done_log = s->done_log;
-  r.log_ld = s->log_ld;
-  r.return_out = s->return_out;
-  r.T = H;
-  r.auto_reset = auto_reset ? 1u : 0u;
-  r.seed_lo = (uint32_t)s->seed;
-  r.seed_hi = (uint32_t)(s->seed >> 32);
-  r.radius = h->cfg.radius;
+  // the commit: steps 0..H-1 of the plane each env's evaluation chose (nt_loads stays 0: the evaluation has just read these rows)
+  TapeArgs r = tape_args(s, s->actions, s->ld, H);
   r.best = s->best_out;
   r.cand_stride = s->cand_stride;
-  launch_tape_select(h, h->args, r);
-  h->args.flags &= ~kFlagWholeGoals;  // tape angles are anybody's floats
-  h->codes_valid = false;             // the kernel writes targets as floats only
-  return check_launch(h, "rollout_tape_kernel<SELECT>");
+  return commit_tape(h, r, s->seed, auto_reset, true);
 }
-
-namespace {
-// what mt_cem and mt_sample_plans both read of a struct mt_cem: the candidate stream's parameters
-int cem_stream_args(mt_handle h, const struct mt_cem* s, const char* who, CemArgs& e) {
-  const std::string w(who);
-  MT_REQUIRE(h, s->n_steps >= 0 && s->n_steps <= 65535, w + ": mt_cem.n_steps must be 0..65535");
-  MT_REQUIRE(h, s->n_candidates >= 1 && s->n_candidates <= 64, w + ": mt_cem.n_candidates must be 1..64");
-  MT_REQUIRE(h, (s->flags & ~(MT_CEM_AUTO_RESET | MT_CEM_KEEP_MEAN)) == 0, w + ": mt_cem.flags: unknown MT_CEM_* flag");
-  // (bit patterns: the build is -ffinite-math-only; 0x47000000 = 32768.0f, the largest angle a step accepts)
-  MT_REQUIRE(h, first_unusable(&s->lo, 1, 0x47000000u) < 0 && first_unusable(&s->hi, 1, 0x47000000u) < 0,
-             w + ": mt_cem.lo / hi must be finite and within +-32768 degrees");
-  MT_REQUIRE(h, s->lo <= s->hi, w + ": mt_cem.lo must be <= hi");
-  e.mean = s->mean;
-  e.sigma = s->sigma;
-  e.ld = s->ld;
-  e.T = s->n_steps;
-  e.C = s->n_candidates;
-  e.draw = s->draw;
-  e.keep_mean = (s->flags & MT_CEM_KEEP_MEAN) ? 1u : 0u;
-  e.seed_lo = (uint32_t)s->seed;
-  e.seed_hi = (uint32_t)(s->seed >> 32);
-  e.lo = s->lo;
-  e.hi = s->hi;
-  return MT_OK;
-}
-// do [p, p + rows * ld) and [q, q + rows2 * ld2) share a byte?  (rows of n floats, the last one not padded)
-bool rows_overlap(const float* p, int64_t rows, int64_t ld, const float* q, int64_t rows2, int64_t ld2, int64_t n) {
-  if (!p || !q || rows == 0 || rows2 == 0) return false;
-  const uintptr_t a0 = (uintptr_t)p, a1 = a0 + (uintptr_t)(((rows - 1) * ld + n) * 4);
-  const uintptr_t b0 = (uintptr_t)q, b1 = b0 + (uintptr_t)(((rows2 - 1) * ld2 + n) * 4);
-  return a0 < b1 && b0 < a1;
-}
-}  // namespace
 
 int mt_sample_plans(mt_handle h, const struct mt_cem* s, void* plans_out, int64_t ld, int64_t cand_stride) {
   MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
   MT_REQUIRE(h, s != nullptr, "mt_sample_plans: cem is NULL");
   CemArgs e{};
-  int rc = cem_stream_args(h, s, "mt_sample_plans", e);
+  int rc = stream_args(h, s, "mt_sample_plans: ", kCemNames, e);
   if (rc) return rc;
   if (s->n_steps == 0) return MT_OK;
-  MT_REQUIRE(h, s->mean != nullptr && s->sigma != nullptr, "mt_sample_plans: mt_cem.mean / sigma is NULL");
-  MT_REQUIRE(h, s->ld >= h->n, "mt_sample_plans: mt_cem.ld is smaller than n_envs");
+  rc = stream_rows(h, s, "mt_sample_plans: ", kCemNames);
+  if (rc) return rc;
   MT_REQUIRE(h, plans_out != nullptr, "mt_sample_plans: plans_out is NULL");
   MT_REQUIRE(h, ld >= h->n, "mt_sample_plans: ld is smaller than n_envs");
   MT_REQUIRE(h, cand_stride >= (int64_t)s->n_steps * h->D * ld, "mt_sample_plans: cand_stride is smaller than n_steps * dof * ld");
@@ -2211,7 +2268,7 @@ int mt_cem(mt_handle h, const struct mt_cem* s) {
   MT_REQUIRE(h, s->struct_size == (int32_t)sizeof(struct mt_cem), "mt_cem.struct_size does not match this library");
   MT_REQUIRE(h, s->reserved == 0, "mt_cem.reserved must be 0");
   CemArgs e{};
-  int rc = cem_stream_args(h, s, "mt_cem", e);
+  int rc = stream_args(h, s, "mt_cem: ", kCemNames, e);
   if (rc) return rc;
   const bool auto_reset = (s->flags & MT_CEM_AUTO_RESET) != 0;
   const int T = s->n_steps, H = s->commit_steps;
@@ -2219,85 +2276,25 @@ int mt_cem(mt_handle h, const struct mt_cem* s) {
   MT_REQUIRE(h, H >= 0 && H <= T, "mt_cem.commit_steps must be 0..n_steps");
   MT_REQUIRE(h, !(auto_reset && H == 0), "MT_CEM_AUTO_RESET with mt_cem.commit_steps == 0: an evaluation re-arms nothing");
   MT_REQUIRE(h, first_unusable(&s->sigma_min, 1, kMaxFiniteBits) < 0 && s->sigma_min >= 0.f, "mt_cem.sigma_min must be finite and >= 0");
-  if (!fusable(h)) {  // the rollout kernels do not implement these
-    const char* what = h->custom_frames ? "custom obs_frame / ee_frame"
-                       : h->trace       ? "MT_FLAG_TRACE"
-                       : h->lds_table   ? "MT_FLAG_DH_IN_LDS"
-                       : h->trig == 2   ? "MT_FLAG_HW_TRIG"
-                       : (h->cfg.flags & MT_FLAG_DIRECT_TRIG) ? "MT_FLAG_DIRECT_TRIG"
-                       : h->trig == 1   ? "substeps beyond the recurrence's reach (per-pose trigonometry)"
-                                        : "a profiling flag (MT_FLAG_ABLATE_*)";
-    return fail(h, MT_ERR_UNSUPPORTED, std::string("mt_cem: not available on a handle with ") + what);
-  }
+  if (!fusable(h)) return fail_unfusable(h, "mt_cem");
   if (!h->is_reset) return fail(h, MT_ERR_STATE, "mt_cem before mt_reset / mt_reset_random");
   if (T == 0) return MT_OK;
-  const int64_t n = h->n, rows = (int64_t)T * h->D;
-  MT_REQUIRE(h, s->mean != nullptr && s->sigma != nullptr, "mt_cem.mean / sigma is NULL");
-  MT_REQUIRE(h, s->ld >= n, "mt_cem.ld is smaller than n_envs");
+  rc = stream_rows(h, s, "", kCemNames);
+  if (rc) return rc;
   MT_REQUIRE(h, (s->mean_out == nullptr) == (s->sigma_out == nullptr), "mt_cem.mean_out and sigma_out: both or neither");
-  MT_REQUIRE(h, !s->mean_out || s->out_ld >= n, "mt_cem.out_ld is smaller than n_envs");
-  MT_REQUIRE(h, !s->returns_out || s->ret_ld >= n, "mt_cem.ret_ld is smaller than n_envs");
-  MT_REQUIRE(h, !(H > 0 && s->chosen_out == nullptr), "mt_cem.chosen_out is NULL with commit_steps > 0");
-  MT_REQUIRE(h, !(H > 0) || s->chosen_ld >= n, "mt_cem.chosen_ld is smaller than n_envs");
-  MT_REQUIRE(h, !(H > 0 && (s->reward_log || s->done_log)) || s->log_ld >= n, "mt_cem.log_ld is smaller than n_envs");
-  // the refit may sit EXACTLY on its input (same base, same pitch: every element is then read and written by one thread);
-  // any other overlap of an output with mean / sigma or with the other output would let one block read another's writes
-  const bool same_m = s->mean_out == s->mean && s->out_ld == s->ld, same_s = s->sigma_out == s->sigma && s->out_ld == s->ld;
-  MT_REQUIRE(h, same_m || !rows_overlap(s->mean_out, rows, s->out_ld, s->mean, rows, s->ld, n), "mt_cem.mean_out overlaps mean without being mean");
-  MT_REQUIRE(h, same_s || !rows_overlap(s->sigma_out, rows, s->out_ld, s->sigma, rows, s->ld, n), "mt_cem.sigma_out overlaps sigma without being sigma");
-  MT_REQUIRE(h, !rows_overlap(s->mean_out, rows, s->out_ld, s->sigma, rows, s->ld, n), "mt_cem.mean_out overlaps sigma");
-  MT_REQUIRE(h, !rows_overlap(s->sigma_out, rows, s->out_ld, s->mean, rows, s->ld, n), "mt_cem.sigma_out overlaps mean");
-  MT_REQUIRE(h, !rows_overlap(s->mean_out, rows, s->out_ld, s->sigma_out, rows, s->out_ld, n), "mt_cem.mean_out overlaps sigma_out");
-  if (H > 0) {
-    const int64_t hr = (int64_t)H * h->D;
-    MT_REQUIRE(h, !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->mean, rows, s->ld, n) &&
-                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->sigma, rows, s->ld, n) &&
-                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->mean_out, rows, s->out_ld, n) &&
-                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->sigma_out, rows, s->out_ld, n),
-               "mt_cem.chosen_out overlaps mean / sigma / mean_out / sigma_out");
-  }
+  rc = refit_args(h, s, kCemNames, e);
+  if (rc) return rc;
   MT_ENTER(h);
-  e.mean_out = s->mean_out;
-  e.sigma_out = s->sigma_out;
-  e.out_ld = s->out_ld;
-  e.returns_out = s->returns_out;
-  e.ret_ld = s->ret_ld;
-  e.best_out = s->best_out;
-  e.best_return_out = s->best_return_out;
   e.elite_mask = reinterpret_cast<unsigned long long*>(s->elite_mask_out);
-  e.chosen_out = H > 0 ? s->chosen_out : nullptr;
-  e.chosen_ld = s->chosen_ld;
   e.E = s->n_elites;
-  e.H = H;
-  e.sigma_min = s->sigma_min;
   e.inv_e = 1.0f / (float)s->n_elites;  // the fp32 nearest to 1 / E
   launch_cem(h, h->args, e);            // reads the state, writes the caller's rows only
   rc = check_launch(h, "cem_kernel");
   if (rc || H == 0) return rc;
   // the commit: mt_rollout_tape(n_steps = H, actions = chosen_out), host bookkeeping included
-  if (auto_reset) {
-    h->args.seed_lo = (uint32_t)s->seed;
-    h->args.seed_hi = (uint32_t)(s->seed >> 32);
-    int rcg = order_behind_inplace_gather(h, h->stream);  // the in-kernel re-arm writes MT_F_LAST_RETURN
-    if (rcg) return rcg;
-  }
-  TapeArgs r{};
-  r.tape = s->chosen_out;
-  r.tape_ld = s->chosen_ld;
-  r.reward_log = s->reward_log;
-  r.done_log = s->done_log;
-  r.log_ld = s->log_ld;
-  r.return_out = s->return_out;
-  r.T = H;
-  r.auto_reset = auto_reset ? 1u : 0u;
+  TapeArgs r = tape_args(s, s->chosen_out, s->chosen_ld, H);
   r.nt_loads = h->tape_nt_loads ? 1u : 0u;
-  r.seed_lo = (uint32_t)s->seed;
-  r.seed_hi = (uint32_t)(s->seed >> 32);
-  r.radius = h->cfg.radius;
-  launch_tape(h, h->args, r);
-  h->args.flags &= ~kFlagWholeGoals;  // drawn angles are anybody's floats
-  h->codes_valid = false;             // the kernel writes targets as floats only
-  return check_launch(h, "rollout_tape_kernel");
+  return commit_tape(h, r, s->seed, auto_reset, false);
 }
 
 int mt_mppi(mt_handle h, const struct mt_mppi* s) {
@@ -2305,14 +2302,9 @@ int mt_mppi(mt_handle h, const struct mt_mppi* s) {
   MT_REQUIRE(h, s != nullptr, "mppi is NULL");
   MT_REQUIRE(h, s->struct_size == (int32_t)sizeof(struct mt_mppi), "mt_mppi.struct_size does not match this library");
   MT_REQUIRE(h, s->reserved == 0, "mt_mppi.reserved must be 0");
-  static_assert(MT_MPPI_MAX_STEPS == kMppiMaxSteps, "the header's horizon limit is the kernel's table size");
-  MT_REQUIRE(h, s->n_steps >= 0 && s->n_steps <= MT_MPPI_MAX_STEPS, "mt_mppi.n_steps must be 0..127");
-  MT_REQUIRE(h, s->n_candidates >= 1 && s->n_candidates <= 64, "mt_mppi.n_candidates must be 1..64");
-  MT_REQUIRE(h, (s->flags & ~(MT_MPPI_AUTO_RESET | MT_MPPI_KEEP_MEAN)) == 0, "mt_mppi.flags: unknown MT_MPPI_* flag");
-  // (bit patterns: the build is -ffinite-math-only; 0x47000000 = 32768.0f, the largest angle a step accepts)
-  MT_REQUIRE(h, first_unusable(&s->lo, 1, 0x47000000u) < 0 && first_unusable(&s->hi, 1, 0x47000000u) < 0,
-             "mt_mppi.lo / hi must be finite and within +-32768 degrees");
-  MT_REQUIRE(h, s->lo <= s->hi, "mt_mppi.lo must be <= hi");
+  MppiArgs e{};
+  int rc = stream_args(h, s, "", kMppiNames, e);
+  if (rc) return rc;
   const bool auto_reset = (s->flags & MT_MPPI_AUTO_RESET) != 0;
   const int T = s->n_steps, H = s->commit_steps;
   MT_REQUIRE(h, H >= 0 && H <= T, "mt_mppi.commit_steps must be 0..n_steps");
@@ -2320,99 +2312,26 @@ int mt_mppi(mt_handle h, const struct mt_mppi* s) {
   MT_REQUIRE(h, first_unusable(&s->sigma_min, 1, kMaxFiniteBits) < 0 && s->sigma_min >= 0.f, "mt_mppi.sigma_min must be finite and >= 0");
   // 0x3F800000 = 1.0f: a NaN, an inf or anything beyond 1 fails the first test, a negative value (not -0) the second
   MT_REQUIRE(h, first_unusable(&s->decay, 1, 0x3F800000u) < 0 && s->decay >= 0.f, "mt_mppi.decay must be finite and within 0..1");
-  if (!fusable(h)) {  // the rollout kernels do not implement these
-    const char* what = h->custom_frames ? "custom obs_frame / ee_frame"
-                       : h->trace       ? "MT_FLAG_TRACE"
-                       : h->lds_table   ? "MT_FLAG_DH_IN_LDS"
-                       : h->trig == 2   ? "MT_FLAG_HW_TRIG"
-                       : (h->cfg.flags & MT_FLAG_DIRECT_TRIG) ? "MT_FLAG_DIRECT_TRIG"
-                       : h->trig == 1   ? "substeps beyond the recurrence's reach (per-pose trigonometry)"
-                                        : "a profiling flag (MT_FLAG_ABLATE_*)";
-    return fail(h, MT_ERR_UNSUPPORTED, std::string("mt_mppi: not available on a handle with ") + what);
-  }
+  if (!fusable(h)) return fail_unfusable(h, "mt_mppi");
   if (!h->is_reset) return fail(h, MT_ERR_STATE, "mt_mppi before mt_reset / mt_reset_random");
   if (T == 0) return MT_OK;
-  const int64_t n = h->n, rows = (int64_t)T * h->D;
-  MT_REQUIRE(h, s->mean != nullptr && s->sigma != nullptr, "mt_mppi.mean / sigma is NULL");
-  MT_REQUIRE(h, s->ld >= n, "mt_mppi.ld is smaller than n_envs");
+  rc = stream_rows(h, s, "", kMppiNames);
+  if (rc) return rc;
   MT_REQUIRE(h, !(s->sigma_out && !s->mean_out), "mt_mppi.sigma_out without mean_out");
-  MT_REQUIRE(h, !s->mean_out || s->out_ld >= n, "mt_mppi.out_ld is smaller than n_envs");
-  MT_REQUIRE(h, !s->returns_out || s->ret_ld >= n, "mt_mppi.ret_ld is smaller than n_envs");
-  MT_REQUIRE(h, !s->weights_out || s->w_ld >= n, "mt_mppi.w_ld is smaller than n_envs");
-  MT_REQUIRE(h, !(H > 0 && s->chosen_out == nullptr), "mt_mppi.chosen_out is NULL with commit_steps > 0");
-  MT_REQUIRE(h, !(H > 0) || s->chosen_ld >= n, "mt_mppi.chosen_ld is smaller than n_envs");
-  MT_REQUIRE(h, !(H > 0 && (s->reward_log || s->done_log)) || s->log_ld >= n, "mt_mppi.log_ld is smaller than n_envs");
-  // mt_cem's in-place rule: an output EXACTLY on its input (same base, same pitch) is read and written by one thread per
-  // element; any other overlap would let one block read another's writes
-  const bool same_m = s->mean_out == s->mean && s->out_ld == s->ld, same_s = s->sigma_out == s->sigma && s->out_ld == s->ld;
-  MT_REQUIRE(h, same_m || !rows_overlap(s->mean_out, rows, s->out_ld, s->mean, rows, s->ld, n), "mt_mppi.mean_out overlaps mean without being mean");
-  MT_REQUIRE(h, same_s || !rows_overlap(s->sigma_out, rows, s->out_ld, s->sigma, rows, s->ld, n), "mt_mppi.sigma_out overlaps sigma without being sigma");
-  MT_REQUIRE(h, !rows_overlap(s->mean_out, rows, s->out_ld, s->sigma, rows, s->ld, n), "mt_mppi.mean_out overlaps sigma");
-  MT_REQUIRE(h, !rows_overlap(s->sigma_out, rows, s->out_ld, s->mean, rows, s->ld, n), "mt_mppi.sigma_out overlaps mean");
-  MT_REQUIRE(h, !rows_overlap(s->mean_out, rows, s->out_ld, s->sigma_out, rows, s->out_ld, n), "mt_mppi.mean_out overlaps sigma_out");
-  if (H > 0) {
-    const int64_t hr = (int64_t)H * h->D;
-    MT_REQUIRE(h, !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->mean, rows, s->ld, n) &&
-                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->sigma, rows, s->ld, n) &&
-                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->mean_out, rows, s->out_ld, n) &&
-                      !rows_overlap(s->chosen_out, hr, s->chosen_ld, s->sigma_out, rows, s->out_ld, n),
-               "mt_mppi.chosen_out overlaps mean / sigma / mean_out / sigma_out");
-  }
+  rc = refit_args(h, s, kMppiNames, e);
+  if (rc) return rc;
   MT_ENTER(h);
-  MppiArgs e{};
-  e.mean = s->mean;
-  e.sigma = s->sigma;
-  e.ld = s->ld;
-  e.mean_out = s->mean_out;
-  e.sigma_out = s->sigma_out;
-  e.out_ld = s->out_ld;
-  e.returns_out = s->returns_out;
-  e.ret_ld = s->ret_ld;
   e.weights_out = s->weights_out;
   e.w_ld = s->w_ld;
   e.weight_sum_out = s->weight_sum_out;
-  e.best_out = s->best_out;
-  e.best_return_out = s->best_return_out;
-  e.chosen_out = H > 0 ? s->chosen_out : nullptr;
-  e.chosen_ld = s->chosen_ld;
-  e.T = T;
-  e.C = s->n_candidates;
-  e.H = H;
-  e.draw = s->draw;
-  e.keep_mean = (s->flags & MT_MPPI_KEEP_MEAN) ? 1u : 0u;
-  e.seed_lo = (uint32_t)s->seed;
-  e.seed_hi = (uint32_t)(s->seed >> 32);
-  e.lo = s->lo;
-  e.hi = s->hi;
-  e.sigma_min = s->sigma_min;
   e.decay = s->decay;
   launch_mppi(h, h->args, e);  // reads the state, writes the caller's rows only
-  int rc = check_launch(h, "mppi_kernel");
+  rc = check_launch(h, "mppi_kernel");
   if (rc || H == 0) return rc;
   // the commit: mt_rollout_tape(n_steps = H, actions = chosen_out), host bookkeeping included
-  if (auto_reset) {
-    h->args.seed_lo = (uint32_t)s->seed;
-    h->args.seed_hi = (uint32_t)(s->seed >> 32);
-    int rcg = order_behind_inplace_gather(h, h->stream);  // the in-kernel re-arm writes MT_F_LAST_RETURN
-    if (rcg) return rcg;
-  }
-  TapeArgs r{};
-  r.tape = s->chosen_out;
-  r.tape_ld = s->chosen_ld;
-  r.reward_log = s->reward_log;
-  r.done_log = s->done_log;
-  r.log_ld = s->log_ld;
-  r.return_out = s->return_out;
-  r.T = H;
-  r.auto_reset = auto_reset ? 1u : 0u;
+  TapeArgs r = tape_args(s, s->chosen_out, s->chosen_ld, H);
   r.nt_loads = h->tape_nt_loads ? 1u : 0u;
-  r.seed_lo = (uint32_t)s->seed;
-  r.seed_hi = (uint32_t)(s->seed >> 32);
-  r.radius = h->cfg.radius;
-  launch_tape(h, h->args, r);
-  h->args.flags &= ~kFlagWholeGoals;  // drawn angles are anybody's floats
-  h->codes_valid = false;             // the kernel writes targets as floats only
-  return check_launch(h, "rollout_tape_kernel");
+  return commit_tape(h, r, s->seed, auto_reset, false);
 }
 
 int mt_observe(mt_handle h) {

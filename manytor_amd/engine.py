@@ -394,6 +394,87 @@ class StepEngine:
             t = t.permute(0, 1, 3, 2)
         return t.contiguous(), n, steps * d * n
 
+    def _torch_call(self, fn, *args, commits):
+        """A library call that reads and writes torch's memory: on torch's stream (use_torch_stream) it is ordered with the
+        torch ops around it and waits for nothing; on the engine's own stream it waits for torch's current stream before
+        and for its own launch after.  commits: the call changes the resident state."""
+        import torch
+        cur = torch.cuda.current_stream(self.device)
+        ordered = getattr(self, "_caller_stream", None) == int(cur.cuda_stream)   # the engine launches on torch's current stream
+        if not ordered:
+            cur.synchronize()
+        self._call(fn, *args)
+        if not ordered:
+            self.sync()     # the inputs and the outputs are torch's memory: done with before torch may reuse or read it
+        if commits:
+            self.version += 1
+
+    @staticmethod
+    def _commit_steps(commit, auto_reset):
+        """A planner's `commit` as an int; refused ahead of everything else when auto_reset has nothing to re-arm."""
+        commit = int(commit)
+        if auto_reset and commit == 0:
+            raise ValueError("auto_reset needs commit > 0: an evaluation re-arms nothing")
+        return commit
+
+    def _commit_outputs(self, arg, out, T, commit, log, returns, chosen=True):
+        """The commit side of shoot / cem / mppi: `commit` against T, then the outputs of the committed steps into `out` and
+        their addresses into `arg` (`chosen`: the call writes the committed angles as a tape of their own)."""
+        import torch
+        if not 0 <= commit <= T:
+            raise ValueError(f"commit must be 0..T = {T}, got {commit}")
+        n, dev = self.n_envs, out["best"].device
+        arg.commit_steps = commit
+        if chosen:
+            if commit:
+                out["chosen"] = torch.empty((commit, self.dof, n), dtype=torch.float32, device=dev)
+            arg.chosen_out = out["chosen"].data_ptr() if commit else None
+            arg.chosen_ld = n
+        if log:
+            out["reward"] = torch.empty((commit, n), dtype=torch.int8, device=dev)
+            out["done"] = torch.empty((commit, n), dtype=torch.uint8, device=dev)
+        if returns:                                              # (commit == 0: the call writes nothing here)
+            out["returns"] = (torch.empty if commit else torch.zeros)(n, dtype=torch.float32, device=dev)
+        arg.reward_log = out["reward"].data_ptr() if log and commit else None
+        arg.done_log = out["done"].data_ptr() if log and commit else None
+        arg.log_ld = n
+        arg.return_out = out["returns"].data_ptr() if returns and commit else None
+
+    def _refit_args(self, arg, mean, sigma, c, lo, hi, sigma_min, draw, seed, inplace, fit_sigma, all_returns, max_steps=None):
+        """What cem and mppi share ahead of the commit: sigma_min, the horizon (max_steps: the call's own limit, ahead of the
+        tensor checks) and the rows; the candidate stream and the refit's outputs into `arg`.  Returns (out, T, alloc),
+        alloc(shape, dtype=) for the further outputs the kernel writes whenever it runs."""
+        import functools
+        import torch
+        sigma_min = float(sigma_min)
+        if not (np.isfinite(sigma_min) and sigma_min >= 0.0):
+            raise ValueError(f"sigma_min must be finite and >= 0, got {sigma_min}")
+        steps = getattr(mean, "shape", None)
+        if max_steps is not None and steps is not None and len(steps) == 3 and int(steps[0]) > max_steps:
+            raise ValueError(f"at most {max_steps} steps, got {int(steps[0])}")
+        mean, sigma, T, ld = self._cem_rows(mean, sigma)
+        n, d = self.n_envs, self.dof
+        dev = mean.device
+        alloc = functools.partial(torch.empty if T else torch.zeros, device=dev)   # (T == 0: the call is a no-op and writes nothing)
+        out = {"best": alloc(n, dtype=torch.int32), "best_return": alloc(n, dtype=torch.float32)}
+        fitted = ("mean", "sigma") if fit_sigma else ("mean",)
+        for name, t in zip(fitted, (mean, sigma)):
+            out[name] = t if inplace else torch.empty((T, d, n), dtype=torch.float32, device=dev)
+        if all_returns:
+            out["candidate_returns"] = alloc((c, n), dtype=torch.float32)
+        arg.n_steps, arg.n_candidates, arg.draw = T, c, int(draw) & 0xFFFFFFFF
+        arg.mean, arg.sigma, arg.ld = (mean.data_ptr(), sigma.data_ptr(), ld) if T else (None, None, n)
+        arg.mean_out = out["mean"].data_ptr() if T else None
+        arg.sigma_out = out["sigma"].data_ptr() if T and fit_sigma else None
+        arg.out_ld = ld if inplace else n
+        arg.lo, arg.hi, arg.sigma_min = lo, hi, sigma_min
+        arg.returns_out = out["candidate_returns"].data_ptr() if all_returns else None
+        arg.ret_ld = n
+        arg.best_out = out["best"].data_ptr()
+        arg.best_return_out = out["best_return"].data_ptr()
+        arg.seed = int(seed)
+        return out, T, alloc
+
     def rollout_actions(self, actions, *, layout="env_major", auto_reset=False, seed=0x5EED, log=False, returns=False,
                         dry_run=False):
         """T steps with the caller's actions in ONE launch (mt_rollout_tape): `actions` is (T, N, D) degrees
@@ -428,15 +509,7 @@ class StepEngine:
         arg.seed = int(seed)
         arg.flags = (L.TAPE_AUTO_RESET if auto_reset else 0) | (L.TAPE_DRY_RUN if dry_run else 0)
         arg.reserved = 0
-        cur = int(torch.cuda.current_stream(self.device).cuda_stream)
-        ordered = getattr(self, "_caller_stream", None) == cur   # the engine launches on torch's current stream
-        if not ordered:
-            torch.cuda.current_stream(self.device).synchronize()
-        self._call(self._lib.mt_rollout_tape, C.byref(arg))
-        if not ordered:
-            self.sync()     # the tape and the outputs are torch's memory: done with before torch may reuse or read it
-        if not dry_run:
-            self.version += 1
+        self._torch_call(self._lib.mt_rollout_tape, C.byref(arg), commits=not dry_run)
         return out or None
 
     def shoot(self, plans, *, layout="soa", commit=0, auto_reset=False, seed=0x5EED, all_returns=False, log=False,
@@ -451,50 +524,30 @@ class StepEngine:
         int8 and `done` (H, N) uint8 and returns=True their per-env sum `returns` (N,).  Device tensors in a dict.
         Stream rules as rollout_actions; with commit == 0 nothing resident changes."""
         import torch
-        commit = int(commit)
-        if auto_reset and commit == 0:
-            raise ValueError("auto_reset needs commit > 0: an evaluation re-arms nothing")
+        commit = self._commit_steps(commit, auto_reset)
         tape, ld, cand_stride = self._tape_tensor(plans, layout, candidates=True)
         c, T, n = int(tape.shape[0]), int(tape.shape[1]), self.n_envs
         if not 1 <= c <= 64:
             raise ValueError(f"plans must hold 1..64 candidates, got {c}")
-        if not 0 <= commit <= T:
-            raise ValueError(f"commit must be 0..T = {T}, got {commit}")
         dev = tape.device
         alloc = torch.empty if T else torch.zeros                # (T == 0: the call is a no-op and writes nothing)
         out = {"best": alloc(n, dtype=torch.int32, device=dev), "best_return": alloc(n, dtype=torch.float32, device=dev)}
         if all_returns:
             out["candidate_returns"] = alloc((c, n), dtype=torch.float32, device=dev)
-        if log:
-            out["reward"] = torch.empty((commit, n), dtype=torch.int8, device=dev)
-            out["done"] = torch.empty((commit, n), dtype=torch.uint8, device=dev)
-        if returns:
-            out["returns"] = (alloc if commit else torch.zeros)(n, dtype=torch.float32, device=dev)
         arg = L.MtShoot()
         arg.struct_size = C.sizeof(L.MtShoot)
-        arg.n_steps, arg.n_candidates, arg.commit_steps = T, c, commit
+        self._commit_outputs(arg, out, T, commit, log, returns, chosen=False)
+        arg.n_steps, arg.n_candidates = T, c
         arg.actions = tape.data_ptr() if T else None
         arg.ld, arg.cand_stride = ld, cand_stride
         arg.returns_out = out["candidate_returns"].data_ptr() if all_returns else None
         arg.ret_ld = n
         arg.best_out = out["best"].data_ptr()
         arg.best_return_out = out["best_return"].data_ptr()
-        arg.reward_log = out["reward"].data_ptr() if log and commit else None
-        arg.done_log = out["done"].data_ptr() if log and commit else None
-        arg.log_ld = n
-        arg.return_out = out["returns"].data_ptr() if returns and commit else None
         arg.seed = int(seed)
         arg.flags = L.SHOOT_AUTO_RESET if auto_reset else 0
         arg.reserved = 0
-        cur = int(torch.cuda.current_stream(self.device).cuda_stream)
-        ordered = getattr(self, "_caller_stream", None) == cur   # the engine launches on torch's current stream
-        if not ordered:
-            torch.cuda.current_stream(self.device).synchronize()
-        self._call(self._lib.mt_shoot, C.byref(arg))
-        if not ordered:
-            self.sync()     # the plans and the outputs are torch's memory: done with before torch may reuse or read it
-        if commit and T:
-            self.version += 1
+        self._torch_call(self._lib.mt_shoot, C.byref(arg), commits=bool(commit and T))
         return out
 
     def _cem_rows(self, mean, sigma):
@@ -547,14 +600,8 @@ class StepEngine:
         arg.lo, arg.hi = lo, hi
         arg.seed = int(seed)
         arg.flags = L.CEM_KEEP_MEAN if keep_mean else 0
-        cur = int(torch.cuda.current_stream(self.device).cuda_stream)
-        ordered = getattr(self, "_caller_stream", None) == cur
-        if not ordered:
-            torch.cuda.current_stream(self.device).synchronize()
-        self._call(self._lib.mt_sample_plans, C.byref(arg), C.c_void_p(out.data_ptr() if T else None), C.c_int64(n),
-                   C.c_int64(T * d * n))
-        if not ordered:
-            self.sync()
+        self._torch_call(self._lib.mt_sample_plans, C.byref(arg), C.c_void_p(out.data_ptr() if T else None), C.c_int64(n),
+                         C.c_int64(T * d * n), commits=False)
         return out
 
     def cem(self, mean, sigma, *, candidates, elites, draw=0, seed=0x5EED, commit=0, auto_reset=False, lo=-180., hi=180.,
@@ -571,68 +618,22 @@ class StepEngine:
         keep_mean=True makes candidate 0 the clamped mean.  Stream rules as shoot(); with commit == 0 nothing resident
         changes."""
         import torch
-        commit = int(commit)
-        if auto_reset and commit == 0:
-            raise ValueError("auto_reset needs commit > 0: an evaluation re-arms nothing")
+        commit = self._commit_steps(commit, auto_reset)
         c, lo, hi = self._cem_scalars(candidates, lo, hi)
-        e, sigma_min = int(elites), float(sigma_min)
+        e = int(elites)
         if not 1 <= e <= c:
             raise ValueError(f"elites must be 1..candidates = {c}, got {e}")
-        if not (np.isfinite(sigma_min) and sigma_min >= 0.0):
-            raise ValueError(f"sigma_min must be finite and >= 0, got {sigma_min}")
-        mean, sigma, T, ld = self._cem_rows(mean, sigma)
-        if not 0 <= commit <= T:
-            raise ValueError(f"commit must be 0..T = {T}, got {commit}")
-        n, d = self.n_envs, self.dof
-        dev = mean.device
-        alloc = torch.empty if T else torch.zeros                # (T == 0: the call is a no-op and writes nothing)
-        out = {"best": alloc(n, dtype=torch.int32, device=dev), "best_return": alloc(n, dtype=torch.float32, device=dev)}
-        if inplace:
-            out["mean"], out["sigma"], out_ld = mean, sigma, ld
-        else:
-            out["mean"], out["sigma"], out_ld = torch.empty((T, d, n), dtype=torch.float32, device=dev), \
-                torch.empty((T, d, n), dtype=torch.float32, device=dev), n
-        if all_returns:
-            out["candidate_returns"] = alloc((c, n), dtype=torch.float32, device=dev)
-        if elite_mask:
-            out["elite_mask"] = alloc(n, dtype=torch.int64, device=dev)
-        if commit:
-            out["chosen"] = torch.empty((commit, d, n), dtype=torch.float32, device=dev)
-        if log:
-            out["reward"] = torch.empty((commit, n), dtype=torch.int8, device=dev)
-            out["done"] = torch.empty((commit, n), dtype=torch.uint8, device=dev)
-        if returns:
-            out["returns"] = (alloc if commit else torch.zeros)(n, dtype=torch.float32, device=dev)
         arg = L.MtCem()
         arg.struct_size = C.sizeof(L.MtCem)
-        arg.n_steps, arg.n_candidates, arg.n_elites, arg.commit_steps = T, c, e, commit
-        arg.draw = int(draw) & 0xFFFFFFFF
-        arg.mean, arg.sigma, arg.ld = (mean.data_ptr(), sigma.data_ptr(), ld) if T else (None, None, n)
-        arg.mean_out, arg.sigma_out, arg.out_ld = (out["mean"].data_ptr(), out["sigma"].data_ptr(), out_ld) if T else (None, None, n)
-        arg.lo, arg.hi, arg.sigma_min = lo, hi, sigma_min
-        arg.returns_out = out["candidate_returns"].data_ptr() if all_returns else None
-        arg.ret_ld = n
-        arg.best_out = out["best"].data_ptr()
-        arg.best_return_out = out["best_return"].data_ptr()
+        out, T, alloc = self._refit_args(arg, mean, sigma, c, lo, hi, sigma_min, draw, seed, inplace, True, all_returns)
+        if elite_mask:
+            out["elite_mask"] = alloc(self.n_envs, dtype=torch.int64)
+        self._commit_outputs(arg, out, T, commit, log, returns)
+        arg.n_elites = e
         arg.elite_mask_out = out["elite_mask"].data_ptr() if elite_mask else None
-        arg.chosen_out = out["chosen"].data_ptr() if commit else None
-        arg.chosen_ld = n
-        arg.reward_log = out["reward"].data_ptr() if log and commit else None
-        arg.done_log = out["done"].data_ptr() if log and commit else None
-        arg.log_ld = n
-        arg.return_out = out["returns"].data_ptr() if returns and commit else None
-        arg.seed = int(seed)
         arg.flags = (L.CEM_AUTO_RESET if auto_reset else 0) | (L.CEM_KEEP_MEAN if keep_mean else 0)
         arg.reserved = 0
-        cur = int(torch.cuda.current_stream(self.device).cuda_stream)
-        ordered = getattr(self, "_caller_stream", None) == cur   # the engine launches on torch's current stream
-        if not ordered:
-            torch.cuda.current_stream(self.device).synchronize()
-        self._call(self._lib.mt_cem, C.byref(arg))
-        if not ordered:
-            self.sync()     # mean, sigma and the outputs are torch's memory: done with before torch may reuse or read it
-        if commit and T:
-            self.version += 1
+        self._torch_call(self._lib.mt_cem, C.byref(arg), commits=bool(commit and T))
         return out
 
     def mppi(self, mean, sigma, *, candidates, temperature=None, decay=None, draw=0, seed=0x5EED, commit=0, auto_reset=False,
@@ -651,9 +652,7 @@ class StepEngine:
         those angles, log=True adds `reward` / `done` (H, N) and returns=True `returns` (N,).  At most 127 steps.  Stream
         rules as cem(); with commit == 0 nothing resident changes."""
         import torch
-        commit = int(commit)
-        if auto_reset and commit == 0:
-            raise ValueError("auto_reset needs commit > 0: an evaluation re-arms nothing")
+        commit = self._commit_steps(commit, auto_reset)
         c, lo, hi = self._cem_scalars(candidates, lo, hi)
         if (temperature is None) == (decay is None):
             raise ValueError("give exactly one of temperature and decay")
@@ -667,74 +666,22 @@ class StepEngine:
             if not (np.isfinite(rho) and 0.0 <= rho <= 1.0):
                 raise ValueError(f"decay must be finite and within 0..1, got {rho}")
             rho = float(np.float32(rho))
-        sigma_min = float(sigma_min)
-        if not (np.isfinite(sigma_min) and sigma_min >= 0.0):
-            raise ValueError(f"sigma_min must be finite and >= 0, got {sigma_min}")
-        steps = getattr(mean, "shape", None)                     # (ahead of the tensor checks: the horizon is the call's own limit)
-        if steps is not None and len(steps) == 3 and int(steps[0]) > L.MPPI_MAX_STEPS:
-            raise ValueError(f"at most {L.MPPI_MAX_STEPS} steps, got {int(steps[0])}")
-        mean, sigma, T, ld = self._cem_rows(mean, sigma)
-        if not 0 <= commit <= T:
-            raise ValueError(f"commit must be 0..T = {T}, got {commit}")
-        n, d = self.n_envs, self.dof
-        dev = mean.device
-        alloc = torch.empty if T else torch.zeros                # (T == 0: the call is a no-op and writes nothing)
-        out = {"best": alloc(n, dtype=torch.int32, device=dev), "best_return": alloc(n, dtype=torch.float32, device=dev),
-               "weight_sum": alloc(n, dtype=torch.float32, device=dev)}
-        if inplace:
-            out["mean"], out_ld = mean, ld
-            if fit_sigma:
-                out["sigma"] = sigma
-        else:
-            out["mean"], out_ld = torch.empty((T, d, n), dtype=torch.float32, device=dev), n
-            if fit_sigma:
-                out["sigma"] = torch.empty((T, d, n), dtype=torch.float32, device=dev)
-        if all_returns:
-            out["candidate_returns"] = alloc((c, n), dtype=torch.float32, device=dev)
-        if weights:
-            out["weights"] = alloc((c, n), dtype=torch.float32, device=dev)
-        if commit:
-            out["chosen"] = torch.empty((commit, d, n), dtype=torch.float32, device=dev)
-        if log:
-            out["reward"] = torch.empty((commit, n), dtype=torch.int8, device=dev)
-            out["done"] = torch.empty((commit, n), dtype=torch.uint8, device=dev)
-        if returns:
-            out["returns"] = (alloc if commit else torch.zeros)(n, dtype=torch.float32, device=dev)
         arg = L.MtMppi()
         arg.struct_size = C.sizeof(L.MtMppi)
-        arg.n_steps, arg.n_candidates, arg.commit_steps = T, c, commit
-        arg.draw = int(draw) & 0xFFFFFFFF
+        out, T, alloc = self._refit_args(arg, mean, sigma, c, lo, hi, sigma_min, draw, seed, inplace, fit_sigma, all_returns,
+                                         max_steps=L.MPPI_MAX_STEPS)
+        n = self.n_envs
+        out["weight_sum"] = alloc(n, dtype=torch.float32)
+        if weights:
+            out["weights"] = alloc((c, n), dtype=torch.float32)
+        self._commit_outputs(arg, out, T, commit, log, returns)
         arg.decay = rho
-        arg.mean, arg.sigma, arg.ld = (mean.data_ptr(), sigma.data_ptr(), ld) if T else (None, None, n)
-        arg.mean_out = out["mean"].data_ptr() if T else None
-        arg.sigma_out = out["sigma"].data_ptr() if T and fit_sigma else None
-        arg.out_ld = out_ld
-        arg.lo, arg.hi, arg.sigma_min = lo, hi, sigma_min
-        arg.returns_out = out["candidate_returns"].data_ptr() if all_returns else None
-        arg.ret_ld = n
         arg.weights_out = out["weights"].data_ptr() if weights else None
         arg.w_ld = n
         arg.weight_sum_out = out["weight_sum"].data_ptr()
-        arg.best_out = out["best"].data_ptr()
-        arg.best_return_out = out["best_return"].data_ptr()
-        arg.chosen_out = out["chosen"].data_ptr() if commit else None
-        arg.chosen_ld = n
-        arg.reward_log = out["reward"].data_ptr() if log and commit else None
-        arg.done_log = out["done"].data_ptr() if log and commit else None
-        arg.log_ld = n
-        arg.return_out = out["returns"].data_ptr() if returns and commit else None
-        arg.seed = int(seed)
         arg.flags = (L.MPPI_AUTO_RESET if auto_reset else 0) | (L.MPPI_KEEP_MEAN if keep_mean else 0)
         arg.reserved = 0
-        cur = int(torch.cuda.current_stream(self.device).cuda_stream)
-        ordered = getattr(self, "_caller_stream", None) == cur   # the engine launches on torch's current stream
-        if not ordered:
-            torch.cuda.current_stream(self.device).synchronize()
-        self._call(self._lib.mt_mppi, C.byref(arg))
-        if not ordered:
-            self.sync()     # mean, sigma and the outputs are torch's memory: done with before torch may reuse or read it
-        if commit and T:
-            self.version += 1
+        self._torch_call(self._lib.mt_mppi, C.byref(arg), commits=bool(commit and T))
         return out
 
     def observe(self):
