@@ -2523,7 +2523,8 @@ __global__ __launch_bounds__(kBlock) void rollout_tape_kernel(const StepArgs a, 
 //   targets : one READ-ONLY [3K][64] LDS tile shared by the four waves (24 KB at K = 32).  The dry run's dead-target
 //             zeroing serves the observation of a committing call; no return depends on it, so there is no
 //             per-candidate copy.
-//   a step  : what the tape kernel's intermediate steps run -- unusable_angle screening (held pose, NOT counted),
+//   a step  : plan_step, shared with cem_kernel and mppi_kernel: every bit identity between the three rests on that one
+//             text.  It is what the tape kernel's intermediate steps run -- unusable_angle screening (held pose, NOT counted),
 //             route_kinematics<Tbl, 0, true, false> with the PoseCache kept across the steps of one candidate, within_box
 //             on the alive targets, the reward rule.  MT_FLAG_TERMINATE_ON_GROUND changes `done` only, and without a
 //             re-arm `done` feeds nothing a return depends on: there is nothing to compute for it.
@@ -2545,6 +2546,49 @@ struct ShootArgs {
   int32_t T, C;
 };
 
+// The block prologue of shoot_kernel, cem_kernel and mppi_kernel: a live lane loads its start pose and alive mask, and the
+// four waves fill the [3K][64] target tile.  The barrier that publishes the tile is the caller's.
+template <int D>
+__device__ __forceinline__ void plan_start(const StepArgs& a, bool live, uint32_t lane, uint32_t w, LaneOffset<true>& o4, float* tile,
+                                           float (&g0)[D], uint32_t& am0) {
+  const int64_t ld = a.ld;
+  am0 = 0u;
+  if (live) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) g0[j] = ldr(a.goals + j * ld, o4);
+    am0 = ldr(a.alive, o4);
+    for (int k = (int)w; k < 3 * a.K; k += kShootWaves) tile[k * kShootEnvs + lane] = ldr(a.points + (int64_t)k * ld, o4);
+  }
+}
+
+// One step of one candidate, the only copy: the angles `raw` take pose g, alive mask am, return ret and the PoseCache of
+// this candidate one step on.  `col` is the lane's column of the target tile.
+template <class Tbl>
+__device__ __forceinline__ void plan_step(const Tbl& t, const StepArgs& a, const float (&raw)[Tbl::D], float (&g)[Tbl::D], uint32_t& am,
+                                          float& ret, PoseCache<Tbl::D>& pose, bool& pose_valid, const float* col) {
+  constexpr int D = Tbl::D;
+  float act[D], el[3], e[3];
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < D; ++j) bad |= unusable_angle(raw[j]);
+#pragma unroll
+  for (int j = 0; j < D; ++j) act[j] = bad ? g[j] : raw[j];  // the env holds its pose this step
+
+  const float zmin = route_kinematics<Tbl, 0, true, false>(t, a.S, a.inv_sm1, g, act, el, e, &pose, pose_valid, nullptr, false);
+  pose_valid = true;
+  const bool ground = zmin < 0.f;
+  uint32_t nam = am;
+  for (int k = 0; k < a.K; ++k) {
+    if (!((am >> k) & 1u)) continue;
+    const float* pk = col + 3 * k * kShootEnvs;
+    if (within_box(e, pk[0], pk[kShootEnvs], pk[2 * kShootEnvs], a.tol)) nam &= ~(1u << k);
+  }
+  ret += (float)(ground ? -1 : ((nam != am) ? 1 : 0));
+  am = nam;
+#pragma unroll
+  for (int j = 0; j < D; ++j) g[j] = act[j];
+}
+
 template <class Tbl>
 __global__ __launch_bounds__(kBlock) void shoot_kernel(const StepArgs a, const ShootArgs r) {
   extern __shared__ __attribute__((aligned(16))) float tile[];  // [3K][64] targets, [4][64] best returns, [4][64] best indices
@@ -2554,19 +2598,13 @@ __global__ __launch_bounds__(kBlock) void shoot_kernel(const StepArgs a, const S
   const uint32_t i = blockIdx.x * kShootEnvs + lane;
   const bool live = i < a.n;  // the tail lanes of the last block load, score and store nothing, but meet the barriers
   LaneOffset<true> o4{i * 4u};
-  const int64_t ld = a.ld;
   const float* col = tile + lane;
   float* best_v = tile + 3 * a.K * kShootEnvs;
   int32_t* best_c = reinterpret_cast<int32_t*>(best_v + kShootWaves * kShootEnvs);
 
   float g0[D];
-  uint32_t am0 = 0u;
-  if (live) {
-#pragma unroll
-    for (int j = 0; j < D; ++j) g0[j] = ldr(a.goals + j * ld, o4);
-    am0 = ldr(a.alive, o4);
-    for (int k = (int)w; k < 3 * a.K; k += kShootWaves) tile[k * kShootEnvs + lane] = ldr(a.points + (int64_t)k * ld, o4);
-  }
+  uint32_t am0;
+  plan_start<D>(a, live, lane, w, o4, tile, g0, am0);
   __syncthreads();
 
   float top = -__builtin_inff();  // (a return is a finite sum of -1 / 0 / +1)
@@ -2582,28 +2620,10 @@ __global__ __launch_bounds__(kBlock) void shoot_kernel(const StepArgs a, const S
       PoseCache<D> pose;
       bool pose_valid = false;
       for (int s = 0; s < r.T; ++s) {
-        float act[D], raw[D], el[3], e[3];
+        float raw[D];
 #pragma unroll
         for (int j = 0; j < D; ++j) raw[j] = tape_load(plane + ((int64_t)s * D + j) * r.ld, o4, false);
-        bool bad = false;
-#pragma unroll
-        for (int j = 0; j < D; ++j) bad |= unusable_angle(raw[j]);
-#pragma unroll
-        for (int j = 0; j < D; ++j) act[j] = bad ? g[j] : raw[j];  // the env holds its pose this step
-
-        const float zmin = route_kinematics<Tbl, 0, true, false>(t, a.S, a.inv_sm1, g, act, el, e, &pose, pose_valid, nullptr, false);
-        pose_valid = true;
-        const bool ground = zmin < 0.f;
-        uint32_t nam = am;
-        for (int k = 0; k < a.K; ++k) {
-          if (!((am >> k) & 1u)) continue;
-          const float* pk = col + 3 * k * kShootEnvs;
-          if (within_box(e, pk[0], pk[kShootEnvs], pk[2 * kShootEnvs], a.tol)) nam &= ~(1u << k);
-        }
-        ret += (float)(ground ? -1 : ((nam != am) ? 1 : 0));
-        am = nam;
-#pragma unroll
-        for (int j = 0; j < D; ++j) g[j] = act[j];
+        plan_step<Tbl>(t, a, raw, g, am, ret, pose, pose_valid, col);
       }
       if (r.returns_out) str_stream(r.returns_out + (int64_t)c * r.ret_ld, o4, ret);
       if (ret > top) {  // ascending c: a tie keeps the earlier candidate
@@ -2634,7 +2654,8 @@ __global__ __launch_bounds__(kBlock) void shoot_kernel(const StepArgs a, const S
 // (C, T, D, N) block are DRAWN here -- a candidate angle is a pure function of (seed, global env id, draw, c, t, j) and
 // of the env's mean and sigma (philox.h: the plan stream) -- so the block never exists; mt_sample_plans
 // (sample_plans_kernel) writes it out for whoever wants it, and the evaluation below equals shoot_kernel on that block
-// bit for bit: same block / wave / lane shape (a wave = 64 consecutive envs of ONE candidate), same step.
+// bit for bit: same block / wave / lane shape (a wave = 64 consecutive envs of ONE candidate, plan_start), same step
+// (plan_step).
 //   an angle : x = mean + sigma * z (two roundings; contraction is off); unusable_angle(x) is handed on as it is (the
 //              step holds the pose), anything else is clamped to [lo, hi].  KEEP_MEAN: candidate 0 has z = 0.
 //   scores   : every candidate's return goes into a [C][64] LDS tile as well.  Behind the barrier each wave ranks ITS
@@ -2645,7 +2666,7 @@ __global__ __launch_bounds__(kBlock) void shoot_kernel(const StepArgs a, const S
 //              elites in ascending index order (lowest set bit first) -- twice, first for the mean, then for the squared
 //              deviations, nothing is stored -- and writes mean_out / sigma_out[t][.][i].  With mean_out == mean the
 //              element is read and written by this one thread, after the block's last scoring read.  The same pass
-//              writes rows t < H of chosen_out from the best candidate.
+//              writes rows t < H of chosen_out from the best candidate (refit_head, shared with mppi_kernel).
 // No atomics on global memory, no init pass, no dependence between blocks.  Tail lanes meet every barrier and store nothing.
 // ---------------------------------------------------------------------------
 struct CemArgs {
@@ -2690,6 +2711,23 @@ __device__ __forceinline__ void plan_angles(const Args& r, uint64_t seed, uint64
   }
 }
 
+// The head of step s in cem_kernel's and mppi_kernel's refit loops: the env's mean / sigma rows of that step and, where
+// `pick` is set (s < H), row s of chosen_out from the best candidate top_c (x is scratch; the caller reuses it).
+template <int D, class Args>
+__device__ __forceinline__ void refit_head(const Args& r, uint64_t seed, uint64_t env_id, int32_t top_c, int s, bool pick,
+                                           LaneOffset<true>& o4, float (&mu)[D], float (&sg)[D], float (&x)[D]) {
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    mu[j] = tape_load(r.mean + ((int64_t)s * D + j) * r.ld, o4, false);
+    sg[j] = tape_load(r.sigma + ((int64_t)s * D + j) * r.ld, o4, false);
+  }
+  if (pick) {
+    plan_angles<D>(r, seed, env_id, (uint32_t)top_c, (uint32_t)s, mu, sg, x);
+#pragma unroll
+    for (int j = 0; j < D; ++j) str(r.chosen_out + ((int64_t)s * D + j) * r.chosen_ld, o4, x[j]);
+  }
+}
+
 template <int D>
 __global__ __launch_bounds__(kBlock) void sample_plans_kernel(const CemArgs r, float* plans, int64_t ld, int64_t cand_stride, int64_t n,
                                                               int64_t env_base) {
@@ -2720,7 +2758,6 @@ __global__ __launch_bounds__(kBlock) void cem_kernel(const StepArgs a, const Cem
   const uint32_t i = blockIdx.x * kShootEnvs + lane;
   const bool live = i < a.n;
   LaneOffset<true> o4{i * 4u};
-  const int64_t ld = a.ld;
   const float* col = tile + lane;
   float* rets = tile + 3 * a.K * kShootEnvs;
   unsigned long long* masks = reinterpret_cast<unsigned long long*>(rets + r.C * kShootEnvs);
@@ -2729,13 +2766,8 @@ __global__ __launch_bounds__(kBlock) void cem_kernel(const StepArgs a, const Cem
   const uint64_t env_id = (uint64_t)(a.env_base + i);
 
   float g0[D];
-  uint32_t am0 = 0u;
-  if (live) {
-#pragma unroll
-    for (int j = 0; j < D; ++j) g0[j] = ldr(a.goals + j * ld, o4);
-    am0 = ldr(a.alive, o4);
-    for (int k = (int)w; k < 3 * a.K; k += kShootWaves) tile[k * kShootEnvs + lane] = ldr(a.points + (int64_t)k * ld, o4);
-  }
+  uint32_t am0;
+  plan_start<D>(a, live, lane, w, o4, tile, g0, am0);
   __syncthreads();
 
   // ---- score: shoot_kernel's loop with the drawn angles in place of the tape's ----
@@ -2749,32 +2781,14 @@ __global__ __launch_bounds__(kBlock) void cem_kernel(const StepArgs a, const Cem
       PoseCache<D> pose;
       bool pose_valid = false;
       for (int s = 0; s < r.T; ++s) {
-        float act[D], raw[D], mu[D], sg[D], el[3], e[3];
+        float raw[D], mu[D], sg[D];
 #pragma unroll
         for (int j = 0; j < D; ++j) {  // requested at the head of the step: the Philox rounds below cover the latency
           mu[j] = tape_load(r.mean + ((int64_t)s * D + j) * r.ld, o4, false);
           sg[j] = tape_load(r.sigma + ((int64_t)s * D + j) * r.ld, o4, false);
         }
         plan_angles<D>(r, seed, env_id, (uint32_t)c, (uint32_t)s, mu, sg, raw);
-        bool bad = false;
-#pragma unroll
-        for (int j = 0; j < D; ++j) bad |= unusable_angle(raw[j]);
-#pragma unroll
-        for (int j = 0; j < D; ++j) act[j] = bad ? g[j] : raw[j];  // the env holds its pose this step
-
-        const float zmin = route_kinematics<Tbl, 0, true, false>(t, a.S, a.inv_sm1, g, act, el, e, &pose, pose_valid, nullptr, false);
-        pose_valid = true;
-        const bool ground = zmin < 0.f;
-        uint32_t nam = am;
-        for (int k = 0; k < a.K; ++k) {
-          if (!((am >> k) & 1u)) continue;
-          const float* pk = col + 3 * k * kShootEnvs;
-          if (within_box(e, pk[0], pk[kShootEnvs], pk[2 * kShootEnvs], a.tol)) nam &= ~(1u << k);
-        }
-        ret += (float)(ground ? -1 : ((nam != am) ? 1 : 0));
-        am = nam;
-#pragma unroll
-        for (int j = 0; j < D; ++j) g[j] = act[j];
+        plan_step<Tbl>(t, a, raw, g, am, ret, pose, pose_valid, col);
       }
       if (r.returns_out) str_stream(r.returns_out + (int64_t)c * r.ret_ld, o4, ret);
       rets[c * kShootEnvs + lane] = ret;
@@ -2816,16 +2830,7 @@ __global__ __launch_bounds__(kBlock) void cem_kernel(const StepArgs a, const Cem
     const bool pick = s < r.H;
     if (!refit && !pick) break;  // (H <= T and s ascends: nothing further down either)
     float mu[D], sg[D], x[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-      mu[j] = tape_load(r.mean + ((int64_t)s * D + j) * r.ld, o4, false);
-      sg[j] = tape_load(r.sigma + ((int64_t)s * D + j) * r.ld, o4, false);
-    }
-    if (pick) {
-      plan_angles<D>(r, seed, env_id, (uint32_t)top_c, (uint32_t)s, mu, sg, x);
-#pragma unroll
-      for (int j = 0; j < D; ++j) str(r.chosen_out + ((int64_t)s * D + j) * r.chosen_ld, o4, x[j]);
-    }
+    refit_head<D>(r, seed, env_id, top_c, s, pick, o4, mu, sg, x);
     if (!refit) continue;
     float m[D] = {}, v[D] = {};  // (both overwritten by the first elite: the sums start from x_0 and d_0 * d_0)
     unsigned long long left = elite;
@@ -2858,10 +2863,11 @@ __global__ __launch_bounds__(kBlock) void cem_kernel(const StepArgs a, const Cem
   }
 }
 
-// The return of drawn candidate c over r.T steps from the start pose g0 and alive mask am0: cem_kernel's scoring loop,
-// statement for statement, as a function (Args: any block with mean / sigma / ld / T and plan_angles' fields).  cem_kernel
-// itself keeps the loop written out: routed through this function it compiles to one VGPR more in every instantiation
-// (the callee is simplified on its own before it is inlined), and its register rows are pinned.
+// The return of drawn candidate c over r.T steps from the start pose g0 and alive mask am0, for mppi_kernel (Args: any
+// block with mean / sigma / ld / T and plan_angles' fields).  The step exists once, as plan_step; the dozen lines around it
+// -- restart from (g0, am0), load mean / sigma, draw, step -- exist twice, here and in cem_kernel.  Routed through this
+// function cem_kernel compiles to one VGPR more in every instantiation (the callee is simplified on its own before it is
+// inlined), and the register rows of existing kernels stay as they are.
 template <class Tbl, class Args>
 __device__ __forceinline__ float plan_return(const Tbl& t, const StepArgs& a, const Args& r, uint64_t seed, uint64_t env_id, uint32_t c,
                                              LaneOffset<true> o4, const float (&g0)[Tbl::D], uint32_t am0, const float* col) {
@@ -2874,40 +2880,22 @@ __device__ __forceinline__ float plan_return(const Tbl& t, const StepArgs& a, co
   PoseCache<D> pose;
   bool pose_valid = false;
   for (int s = 0; s < r.T; ++s) {
-    float act[D], raw[D], mu[D], sg[D], el[3], e[3];
+    float raw[D], mu[D], sg[D];
 #pragma unroll
     for (int j = 0; j < D; ++j) {  // requested at the head of the step: the Philox rounds below cover the latency
       mu[j] = tape_load(r.mean + ((int64_t)s * D + j) * r.ld, o4, false);
       sg[j] = tape_load(r.sigma + ((int64_t)s * D + j) * r.ld, o4, false);
     }
     plan_angles<D>(r, seed, env_id, c, (uint32_t)s, mu, sg, raw);
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < D; ++j) bad |= unusable_angle(raw[j]);
-#pragma unroll
-    for (int j = 0; j < D; ++j) act[j] = bad ? g[j] : raw[j];  // the env holds its pose this step
-
-    const float zmin = route_kinematics<Tbl, 0, true, false>(t, a.S, a.inv_sm1, g, act, el, e, &pose, pose_valid, nullptr, false);
-    pose_valid = true;
-    const bool ground = zmin < 0.f;
-    uint32_t nam = am;
-    for (int k = 0; k < a.K; ++k) {
-      if (!((am >> k) & 1u)) continue;
-      const float* pk = col + 3 * k * kShootEnvs;
-      if (within_box(e, pk[0], pk[kShootEnvs], pk[2 * kShootEnvs], a.tol)) nam &= ~(1u << k);
-    }
-    ret += (float)(ground ? -1 : ((nam != am) ? 1 : 0));
-    am = nam;
-#pragma unroll
-    for (int j = 0; j < D; ++j) g[j] = act[j];
+    plan_step<Tbl>(t, a, raw, g, am, ret, pose, pose_valid, col);
   }
   return ret;
 }
 
 // ---------------------------------------------------------------------------
 // mt_mppi: one MPPI (model-predictive path integral) iteration where the data sits.  cem_kernel's shape and scoring --
-// the same plan stream, the same block / wave / lane layout, plan_return -- so the evaluation equals shoot_kernel on the
-// block mt_sample_plans writes, bit for bit.  There is no elite set: candidate c weighs rho^k, k = best return - its own.
+// the same plan stream, the same block / wave / lane layout (plan_start), the same step (plan_step, through plan_return)
+// -- so the evaluation equals shoot_kernel on the block mt_sample_plans writes, bit for bit.  There is no elite set: candidate c weighs rho^k, k = best return - its own.
 //   weights  : a step's reward is -1, 0 or +1, so a return is an integer in [-T, T] and the gap k an integer in [0, 2T].
 //              W[0] = 1, W[k] = W[k-1] * rho (one rounding each) is built by thread 0 in LDS ahead of the first barrier;
 //              no transcendental function is evaluated and numpy restates the table bit for bit.
@@ -2920,7 +2908,7 @@ __device__ __forceinline__ float plan_return(const Tbl& t, const StepArgs& a, co
 //              accumulates Q += w_c * (x_c - m)^2 and sigma_out = max(sqrt(Q / S), sigma_min).  A candidate whose weight
 //              is 0 in every lane of the wave is skipped: its terms are +-0 on sums that started from +0.  With mean_out
 //              == mean the element is read and written by this one thread, after the block's last scoring read.  The same
-//              pass writes rows t < H of chosen_out from the best candidate.
+//              pass writes rows t < H of chosen_out from the best candidate (refit_head).
 // No atomics on global memory, no init pass, no dependence between blocks.  Tail lanes meet every barrier and store nothing.
 // ---------------------------------------------------------------------------
 constexpr int kMppiMaxSteps = 127;
@@ -2955,7 +2943,6 @@ __global__ __launch_bounds__(kBlock) void mppi_kernel(const StepArgs a, const Mp
   const uint32_t i = blockIdx.x * kShootEnvs + lane;
   const bool live = i < a.n;
   LaneOffset<true> o4{i * 4u};
-  const int64_t ld = a.ld;
   const float* col = tile + lane;
   float* rets = tile + 3 * a.K * kShootEnvs;
   float* table = rets + r.C * kShootEnvs;
@@ -2963,13 +2950,8 @@ __global__ __launch_bounds__(kBlock) void mppi_kernel(const StepArgs a, const Mp
   const uint64_t env_id = (uint64_t)(a.env_base + i);
 
   float g0[D];
-  uint32_t am0 = 0u;
-  if (live) {
-#pragma unroll
-    for (int j = 0; j < D; ++j) g0[j] = ldr(a.goals + j * ld, o4);
-    am0 = ldr(a.alive, o4);
-    for (int k = (int)w; k < 3 * a.K; k += kShootWaves) tile[k * kShootEnvs + lane] = ldr(a.points + (int64_t)k * ld, o4);
-  }
+  uint32_t am0;
+  plan_start<D>(a, live, lane, w, o4, tile, g0, am0);
   if (threadIdx.x == 0) {  // the recurrence, nothing else: every weight of the call is one of these 2T + 1 floats
     float p = 1.f;
     table[0] = p;
@@ -3031,16 +3013,7 @@ __global__ __launch_bounds__(kBlock) void mppi_kernel(const StepArgs a, const Mp
     const bool pick = s < r.H;
     if (!refit && !pick) break;  // (H <= T and s ascends: nothing further down either)
     float mu[D], sg[D], x[D];
-#pragma unroll
-    for (int j = 0; j < D; ++j) {
-      mu[j] = tape_load(r.mean + ((int64_t)s * D + j) * r.ld, o4, false);
-      sg[j] = tape_load(r.sigma + ((int64_t)s * D + j) * r.ld, o4, false);
-    }
-    if (pick) {
-      plan_angles<D>(r, seed, env_id, (uint32_t)top_c, (uint32_t)s, mu, sg, x);
-#pragma unroll
-      for (int j = 0; j < D; ++j) str(r.chosen_out + ((int64_t)s * D + j) * r.chosen_ld, o4, x[j]);
-    }
+    refit_head<D>(r, seed, env_id, top_c, s, pick, o4, mu, sg, x);
     if (!refit) continue;
     float m[D] = {}, q[D] = {};
     for (int c = 0; c < r.C; ++c) {
