@@ -294,6 +294,9 @@ __device__ __forceinline__ bool within_box(const float (&e)[3], float x, float y
   return (fabsf(e[0] - x) <= tol) && (fabsf(e[1] - y) <= tol) && (fabsf(e[2] - z) <= tol);
 }
 
+// The alive mask of a fresh episode: bit k set for every target k < K (K <= 32).
+__device__ __forceinline__ uint32_t all_alive_mask(int K) { return (K >= 32) ? 0xFFFFFFFFu : ((1u << K) - 1u); }
+
 // A target's coordinates out of its three 21-bit Philox fields (philox.h candidate_fields): x = 2r u(fx) - r,
 // y = 2r u(fy) - r, z = r u(fz).  Contraction is off so that every op rounds once, exactly as the numpy restatement
 // (oracle/philox_ref.py) does.
@@ -1181,7 +1184,7 @@ __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) voi
   uint32_t am = 0;
   float total_in = 0.f;
   if (FRESH) {
-    am = (a.K >= 32) ? 0xFFFFFFFFu : ((1u << a.K) - 1u);
+    am = all_alive_mask(a.K);
   } else if (!kLean || PF) {
     am = ldr(a.alive, o4);
     total_in = ldr(a.total_reward, o4);
@@ -1810,7 +1813,7 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(const StepArgs a, float r
     a.total_reward[i] = 0.f;
     a.reward[i] = 0;
     a.done[i] = 0;
-    uint32_t all_alive = (a.K >= 32) ? 0xFFFFFFFFu : ((1u << a.K) - 1u);
+    uint32_t all_alive = all_alive_mask(a.K);
     if (!RANDOM) {
       // Targets the caller placed (mt_reset; from device memory they cannot be screened on the host): one with a NaN or an
       // infinite coordinate is dropped -- dead from the start, coordinates zeroed, counted with the unusable actions -- instead
@@ -1916,12 +1919,25 @@ __global__ __launch_bounds__(kBlock) void reset_split_kernel(const StepArgs a, f
       a.total_reward[i] = 0.f;
       a.reward[i] = 0;
       a.done[i] = 0;
-      a.alive[i] = (K >= 32) ? 0xFFFFFFFFu : ((1u << K) - 1u);
+      a.alive[i] = all_alive_mask(K);
       a.episodes[i] = episode;
     }
   }
   if (lane == 0) a.done_bits[first >> 6] = 0ull;  // every env of the word has done == 0 after this launch
 }
+
+// One env's column of an LDS target tile [3K][STRIDE], as rollout_kernel and rollout_tape_kernel (STRIDE = kBlock) and
+// rollout_split_kernel (kBlock / L) keep it: coordinate c of target k is col[(3 k + c) * STRIDE].
+template <int STRIDE>
+struct TargetColumn {
+  float* col;
+  __device__ __forceinline__ float& row(int r) const { return col[r * STRIDE]; }  // r = 3 k + c, the row of MT_F_POINTS
+  __device__ __forceinline__ float& cell(int k, int c) const { return row(3 * k + c); }
+  __device__ __forceinline__ float* target(int k) const { return col + 3 * k * STRIDE; }  // x, y, z at [0], [STRIDE], [2 STRIDE]
+  __device__ __forceinline__ void get(int k, float& x, float& y, float& z) const { x = target(k)[0], y = target(k)[STRIDE], z = target(k)[2 * STRIDE]; }
+  __device__ __forceinline__ void put(int k, float x, float y, float z) const { target(k)[0] = x, target(k)[STRIDE] = y, target(k)[2 * STRIDE] = z; }
+  __device__ __forceinline__ void zero(int k) const { put(k, 0.f, 0.f, 0.f); }
+};
 
 // ---------------------------------------------------------------------------
 // rollout: T consecutive Environment.step()s with in-kernel random actions in ONE launch (the inner loop of
@@ -1982,10 +1998,10 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(const StepArgs a, const
   const int64_t ld = a.ld;
   const uint64_t seed = ((uint64_t)a.seed_hi << 32) | a.seed_lo;
   const uint64_t env_id = (uint64_t)(a.env_base + i);
-  float* col = tile + threadIdx.x;
+  const TargetColumn<kBlock> tc{tile + threadIdx.x};
   __shared__ uint8_t draw_slots[kBlock / 64][64];  // draw_targets_wave's scratch (used by launches with reset_first only)
 
-  const uint32_t all_alive = (a.K >= 32) ? 0xFFFFFFFFu : ((1u << a.K) - 1u);
+  const uint32_t all_alive = all_alive_mask(a.K);
   const bool fresh = r.reset_first != 0;  // (wave-uniform: a launch argument)
   float g[D];
 #pragma unroll
@@ -2002,7 +2018,7 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(const StepArgs a, const
     const uint32_t lane = threadIdx.x & 63u;
     draw_targets_wave(((uint64_t)r.reset_seed_hi << 32) | r.reset_seed_lo, (uint64_t)(a.env_base + (i - lane)), episode, mine, a.K, r.radius,
                       tile + (threadIdx.x - lane), draw_slots[threadIdx.x >> 6]);
-    decode_column(col, a.K, r.radius);
+    decode_column(tc.col, a.K, r.radius);
     if (!(kTable && RPF) && !mine) return;
   } else if (RPF) {
 #pragma unroll
@@ -2012,7 +2028,7 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(const StepArgs a, const
         for (int q = 0; q < 3; ++q) tx[k][q] = ldr(a.points + (int64_t)(3 * k + q) * ld, o4);
       }
   } else {
-    for (int k = 0; k < 3 * a.K; ++k) col[k * kBlock] = ldr(a.points + (int64_t)k * ld, o4);
+    for (int k = 0; k < 3 * a.K; ++k) tc.row(k) = ldr(a.points + (int64_t)k * ld, o4);
   }
   PoseCache<D> pose;        // sines / cosines and frame heights of the pose the next step starts from
   bool pose_valid = false;  // nothing known about the pose loaded from memory
@@ -2024,17 +2040,13 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(const StepArgs a, const
 
     uint32_t nam = am;
     for (int k = 0; k < a.K; ++k) {
-      float* pk = col + 3 * k * kBlock;
-      const float x = pk[0], y = pk[kBlock], z = pk[2 * kBlock];
-      const bool al = (am >> k) & 1u;
-      float dist = 0.f, rr = 0.f, th = 0.f;
-      if (al) {
+      float x, y, z, dist = 0.f, rr = 0.f, th = 0.f;
+      tc.get(k, x, y, z);
+      if ((am >> k) & 1u) {
         observe_target(el, x, y, z, dist, rr, th);
         if (within_box(e, x, y, z, a.tol)) nam &= ~(1u << k);
       } else if ((x != 0.f) | (y != 0.f) | (z != 0.f)) {  // manytor.py:148
-        pk[0] = 0.f;
-        pk[kBlock] = 0.f;
-        pk[2 * kBlock] = 0.f;
+        tc.zero(k);
         dirty = true;
       }
       float* orow = a.obs + (int64_t)(3 * k) * ld;
@@ -2066,12 +2078,7 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(const StepArgs a, const
 #pragma unroll
       for (int j = 0; j < D; ++j) g[j] = 0.f;
       pose_valid = false;  // the cache describes the pose the finished episode ended in, not the zero pose
-      draw_targets(seed, env_id, episode, a.K, r.radius, [&](int k, float x, float y, float z) {
-        float* pk = col + 3 * k * kBlock;
-        pk[0] = x;
-        pk[kBlock] = y;
-        pk[2 * kBlock] = z;
-      });
+      draw_targets(seed, env_id, episode, a.K, r.radius, [&](int k, float x, float y, float z) { tc.put(k, x, y, z); });
       dirty = true;
     }
   };
@@ -2093,9 +2100,9 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(const StepArgs a, const
       for (int k = 0; k < RPF; ++k)
         if (k < a.K) {
 #pragma unroll
-          for (int q = 0; q < 3; ++q) col[(3 * k + q) * kBlock] = tx[k][q];
+          for (int q = 0; q < 3; ++q) tc.cell(k, q) = tx[k][q];
         }
-      for (int k = 3 * RPF; k < 3 * a.K; ++k) col[k * kBlock] = ldr(a.points + (int64_t)k * ld, o4);
+      for (int k = 3 * RPF; k < 3 * a.K; ++k) tc.row(k) = ldr(a.points + (int64_t)k * ld, o4);
     }
     finish_step(act, el, e, zmin);
     s = 1;
@@ -2116,7 +2123,7 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(const StepArgs a, const
   if (r.snap) str(r.snap, o4, total);
   if (ended) str(a.episodes, o4, episode);
   if (dirty)
-    for (int k = 0; k < 3 * a.K; ++k) str(a.points + (int64_t)k * ld, o4, col[k * kBlock]);
+    for (int k = 0; k < 3 * a.K; ++k) str(a.points + (int64_t)k * ld, o4, tc.row(k));
 }
 
 // rollout with one env spread over L lanes (L = 2 or 4): rollout_kernel for batches so small that a step's time is one
@@ -2158,10 +2165,10 @@ __global__ __launch_bounds__(kBlock) void rollout_split_kernel(const StepArgs a,
   const int64_t ld = a.ld;
   const uint64_t seed = ((uint64_t)a.seed_hi << 32) | a.seed_lo;
   const uint64_t env_id = (uint64_t)(a.env_base + i);
-  float* col = tile + (threadIdx.x >> 6) * EPW + lane % EPW;
+  const TargetColumn<EPB> tc{tile + (threadIdx.x >> 6) * EPW + lane % EPW};
   const bool backward = (q & 1u) != 0;
 
-  const uint32_t all_alive = (a.K >= 32) ? 0xFFFFFFFFu : ((1u << a.K) - 1u);
+  const uint32_t all_alive = all_alive_mask(a.K);
   const bool fresh = r.reset_first != 0;  // (wave-uniform: a launch argument; see RolloutArgs)
   float g[D];
 #pragma unroll
@@ -2175,10 +2182,7 @@ __global__ __launch_bounds__(kBlock) void rollout_split_kernel(const StepArgs a,
     if (live && q == 0) a.last_return[i] = total;
     total = 0.f;
     draw_targets_split<L>(((uint64_t)r.reset_seed_hi << 32) | r.reset_seed_lo, env_id, episode, true, a.K, r.radius, q, lane % EPW,
-                          [&](int k, TargetCode c) {
-                            float* pk = col + 3 * k * EPB;
-                            decode_target(c, r.radius, pk[0], pk[EPB], pk[2 * EPB]);
-                          });
+                          [&](int k, TargetCode c) { decode_target(c, r.radius, tc.target(k)[0], tc.target(k)[EPB], tc.target(k)[2 * EPB]); });
     __builtin_amdgcn_wave_barrier();  // a target's cells may have been written by another sub-lane of the env (same wave)
   } else if (RPF) {  // this sub-lane's first targets into registers (target index p = q + L * m)
 #pragma unroll
@@ -2194,7 +2198,7 @@ __global__ __launch_bounds__(kBlock) void rollout_split_kernel(const StepArgs a,
     for (int p = (int)q; p < a.K; p += L) {  // this sub-lane's targets into the env's column
       const float* row = a.points + (int64_t)(3 * p) * ld;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) col[(3 * p + c) * EPB] = (row + c * ld)[i];
+      for (int c = 0; c < 3; ++c) tc.cell(p, c) = (row + c * ld)[i];
     }
   }
   PoseCache<D> pose;
@@ -2206,17 +2210,13 @@ __global__ __launch_bounds__(kBlock) void rollout_split_kernel(const StepArgs a,
 
     uint32_t nam = am;
     for (int p = (int)q; p < a.K; p += L) {
-      float* pk = col + 3 * p * EPB;
-      const float x = pk[0], y = pk[EPB], z = pk[2 * EPB];
-      const bool al = (am >> p) & 1u;
-      float dist = 0.f, rr = 0.f, th = 0.f;
-      if (al) {
+      float x, y, z, dist = 0.f, rr = 0.f, th = 0.f;
+      tc.get(p, x, y, z);
+      if ((am >> p) & 1u) {
         observe_target(el, x, y, z, dist, rr, th);
         if (within_box(e, x, y, z, a.tol)) nam &= ~(1u << p);
       } else if ((x != 0.f) | (y != 0.f) | (z != 0.f)) {  // manytor.py:148
-        pk[0] = 0.f;
-        pk[EPB] = 0.f;
-        pk[2 * EPB] = 0.f;
+        tc.zero(p);
         dirty = true;
       }
       if (live) {
@@ -2259,12 +2259,7 @@ __global__ __launch_bounds__(kBlock) void rollout_split_kernel(const StepArgs a,
       for (int j = 0; j < D; ++j) g[j] = 0.f;
       pose_valid = false;
       draw_targets(seed, env_id, episode, a.K, r.radius, [&](int k, float x, float y, float z) {
-        if ((uint32_t)k % L == q) {
-          float* pk = col + 3 * k * EPB;
-          pk[0] = x;
-          pk[EPB] = y;
-          pk[2 * EPB] = z;
-        }
+        if ((uint32_t)k % L == q) tc.put(k, x, y, z);
       });
       dirty = true;
     }
@@ -2287,13 +2282,13 @@ __global__ __launch_bounds__(kBlock) void rollout_split_kernel(const StepArgs a,
         const int p = (int)q + L * m;
         if (p < a.K) {
 #pragma unroll
-          for (int c = 0; c < 3; ++c) col[(3 * p + c) * EPB] = tx[m][c];
+          for (int c = 0; c < 3; ++c) tc.cell(p, c) = tx[m][c];
         }
       }
       for (int p = (int)q + L * PFS; p < a.K; p += L) {
         const float* row = a.points + (int64_t)(3 * p) * ld;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) col[(3 * p + c) * EPB] = (row + c * ld)[i];
+        for (int c = 0; c < 3; ++c) tc.cell(p, c) = (row + c * ld)[i];
       }
     }
     finish_step(act, el, e, zmin);
@@ -2320,7 +2315,7 @@ __global__ __launch_bounds__(kBlock) void rollout_split_kernel(const StepArgs a,
     for (int p = (int)q; p < a.K; p += L) {
       float* row = a.points + (int64_t)(3 * p) * ld;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) (row + c * ld)[i] = col[(3 * p + c) * EPB];
+      for (int c = 0; c < 3; ++c) (row + c * ld)[i] = tc.cell(p, c);
     }
 }
 
@@ -2386,14 +2381,14 @@ __global__ __launch_bounds__(kBlock) void rollout_tape_kernel(const StepArgs a, 
   const int64_t ld = a.ld;
   const uint64_t seed = ((uint64_t)r.seed_hi << 32) | r.seed_lo;
   const uint64_t env_id = (uint64_t)(a.env_base + i);
-  float* col = tile + threadIdx.x;
+  const TargetColumn<kBlock> tc{tile + threadIdx.x};
   const bool commit = r.dry_run == 0;  // (wave-uniform: a launch argument)
   const bool nt = r.nt_loads != 0;
   uint64_t plane = 0;  // byte offset of this env's column in its plane, read once
   if constexpr (SELECT) plane = (uint64_t)(uint32_t)ldr(r.best, o4) * (uint64_t)r.cand_stride * 4u + (uint64_t)i * 4u;
   auto row_load = [&](const float* row) { return SELECT ? tape_load_plane(row, plane) : tape_load(row, o4, nt); };
 
-  const uint32_t all_alive = (a.K >= 32) ? 0xFFFFFFFFu : ((1u << a.K) - 1u);
+  const uint32_t all_alive = all_alive_mask(a.K);
   float g[D], cur[D];
 #pragma unroll
   for (int j = 0; j < D; ++j) cur[j] = row_load(r.tape + (int64_t)j * r.tape_ld);
@@ -2402,7 +2397,7 @@ __global__ __launch_bounds__(kBlock) void rollout_tape_kernel(const StepArgs a, 
   uint32_t am = ldr(a.alive, o4);
   float total = ldr(a.total_reward, o4);
   uint32_t episode = r.auto_reset ? ldr(a.episodes, o4) : 0u;
-  for (int k = 0; k < 3 * a.K; ++k) col[k * kBlock] = ldr(a.points + (int64_t)k * ld, o4);
+  for (int k = 0; k < 3 * a.K; ++k) tc.row(k) = ldr(a.points + (int64_t)k * ld, o4);
   bool ended = false, dirty = false;
   float ret = 0.f;  // sum of this call's rewards, across re-arms
   PoseCache<D> pose;
@@ -2432,17 +2427,13 @@ __global__ __launch_bounds__(kBlock) void rollout_tape_kernel(const StepArgs a, 
 
     uint32_t nam = am;
     for (int k = 0; k < a.K; ++k) {
-      float* pk = col + 3 * k * kBlock;
-      const float x = pk[0], y = pk[kBlock], z = pk[2 * kBlock];
-      const bool al = (am >> k) & 1u;
-      float dist = 0.f, rr = 0.f, th = 0.f;
-      if (al) {
+      float x, y, z, dist = 0.f, rr = 0.f, th = 0.f;
+      tc.get(k, x, y, z);
+      if ((am >> k) & 1u) {
         if (out) observe_target(el, x, y, z, dist, rr, th);
         if (within_box(e, x, y, z, a.tol)) nam &= ~(1u << k);
       } else if ((x != 0.f) | (y != 0.f) | (z != 0.f)) {  // manytor.py:148
-        pk[0] = 0.f;
-        pk[kBlock] = 0.f;
-        pk[2 * kBlock] = 0.f;
+        tc.zero(k);
         dirty = true;
       }
       if (out) {
@@ -2483,12 +2474,7 @@ __global__ __launch_bounds__(kBlock) void rollout_tape_kernel(const StepArgs a, 
 #pragma unroll
       for (int j = 0; j < D; ++j) g[j] = 0.f;
       pose_valid = false;
-      draw_targets(seed, env_id, episode, a.K, r.radius, [&](int k, float x, float y, float z) {
-        float* pk = col + 3 * k * kBlock;
-        pk[0] = x;
-        pk[kBlock] = y;
-        pk[2 * kBlock] = z;
-      });
+      draw_targets(seed, env_id, episode, a.K, r.radius, [&](int k, float x, float y, float z) { tc.put(k, x, y, z); });
       dirty = true;
     }
     if (!PREFETCH && !last) {
@@ -2505,7 +2491,7 @@ __global__ __launch_bounds__(kBlock) void rollout_tape_kernel(const StepArgs a, 
   str(a.total_reward, o4, total);
   if (ended) str(a.episodes, o4, episode);
   if (dirty)
-    for (int k = 0; k < 3 * a.K; ++k) str(a.points + (int64_t)k * ld, o4, col[k * kBlock]);
+    for (int k = 0; k < 3 * a.K; ++k) str(a.points + (int64_t)k * ld, o4, tc.row(k));
 }
 
 // ---------------------------------------------------------------------------
