@@ -40,7 +40,7 @@ extern "C" {
 #define MT_API
 #endif
 
-#define MT_VERSION 430          /* major*10000 + minor*100 + patch */
+#define MT_VERSION 440          /* major*10000 + minor*100 + patch */
 #define MT_MAX_DOF 8
 #define MT_MAX_TARGETS 32
 #define MT_MAX_RETURN_RING 64
@@ -417,6 +417,64 @@ struct mt_mppi {           /* as with mt_cem, the type is always written `struct
   uint32_t flags, reserved;
 };
 MT_API int mt_mppi(mt_handle h, const struct mt_mppi* s);
+
+/* A policy in the loop, in one launch: T x (observe; MLP; step) with the residency of mt_rollout_tape -- pose, alive mask
+ * and return in registers, targets in LDS, the state read and written once per call.  The third action source of the
+ * rollout kernels (in-kernel random draws: mt_rollout_fused; a device tape: mt_rollout_tape; a policy: this call).
+ *
+ * Input.  At every step t the policy of env i sees x, the IN-vector mt_observe would write to MT_F_OBS for the state the
+ * step STARTS from: for target k the triple (dist, r, theta) measured from the observation frame at the current pose,
+ * (0, 0, 0) for a dead target; IN = 3K, with MT_POLICY_SEE_POSE the D joint angles in degrees follow (IN = 3K + D).
+ * After an in-kernel re-arm the current state is the zero pose with the new targets.  NOTE that x is not the obs2 the
+ * previous step returned: a step's observation is taken BEFORE its pickup (manytor.py:91-93), so obs2 still shows the
+ * target the step just picked, while x shows it dead.
+ * Layers.  h_0 = x;  y = W_l h_l + b_l in fp32 (accumulation order and fusing unspecified, but fixed: results are
+ * deterministic and a function of the env's own state, the weights and (seed, global env id, draw, t) -- batch size and
+ * sharding change no bit);  h_{l+1} = hidden_act(y) for l < L-1;  a_j = out_scale * out_act(y_j) for the last layer,
+ * which has D outputs.  tanh is 1 - 2 / (exp(2y) + 1) with hardware exp2 / reciprocal, absolute error < 1e-6.
+ * Weights and biases are device memory and cannot be screened; they are expected to be finite.  A NaN among them goes
+ * through every activation and ends in an unusable action; an infinite weight does the same wherever its input is 0
+ * (0 * inf).  No word outside the (out, in) matrices and (out,) vectors is read, whatever the widths.
+ * Noise.  With sigma_j > 0, a_j += sigma_j * z (an fp32 multiply, then an fp32 add), z the Irwin-Hall variate of mt_cem
+ * (the same byte sum, the same KZ) of word j (j < 4: b = 0) or j - 4 (b = 1) of the Philox-4x32-10 block with counter
+ * (e_lo, e_hi[23:0] | 4 << 24, draw, (b << 16) | t), key = seed: tag 4, a stream of its own.  t counts the steps of the
+ * call and keeps counting across re-arms.
+ * The result is handed on as it is when it is unusable (NaN, +-inf, beyond +-32768 degrees: the env holds its pose for
+ * that step and the pair is counted, as for any tape), else clamped: min(max(a, lo), hi).  action_log gets what was
+ * handed on.
+ * A committing call leaves the handle where mt_rollout_tape leaves it for the same start state, actions = action_log,
+ * the same T and seed, MT_TAPE_AUTO_RESET iff MT_POLICY_AUTO_RESET: every field, the outputs of the last step, the logs,
+ * return_out, ring / MT_F_LAST_RETURN / MT_F_EPISODES and mt_bad_action_count, bit for bit.  MT_POLICY_DRY_RUN writes
+ * the logs, action_log, obs_log and return_out and nothing resident; together with MT_POLICY_AUTO_RESET it is refused.
+ * One launch on the handle's stream, no allocation, no host wait: legal under stream capture.  The weights are read in
+ * stream order; they stay the caller's until then.  MT_ERR_UNSUPPORTED / MT_ERR_STATE as mt_rollout_tape; n_steps == 0
+ * is a no-op; everything the host can see of the struct is screened (MT_ERR_INVALID_ARG). */
+#define MT_POLICY_AUTO_RESET 0x1u   /* re-arm finished envs in the step they finish, as MT_TAPE_AUTO_RESET */
+#define MT_POLICY_DRY_RUN    0x2u   /* evaluate only: logs and return_out are written, nothing resident changes */
+#define MT_POLICY_SEE_POSE   0x4u   /* the D joint angles (degrees) are appended to the policy's input */
+#define MT_POLICY_MAX_LAYERS 3      /* linear layers: at most two hidden ones and the output layer */
+#define MT_POLICY_MAX_WIDTH  64
+enum { MT_ACT_IDENTITY = 0, MT_ACT_TANH = 1, MT_ACT_RELU = 2 };
+struct mt_policy {         /* as with mt_cem, the type is always written `struct mt_policy` */
+  int32_t struct_size;     /* = sizeof(struct mt_policy), checked */
+  int32_t n_steps;         /* T, 0..65535 */
+  int32_t n_layers;        /* L, 1..MT_POLICY_MAX_LAYERS */
+  int32_t width[2];        /* outputs of hidden layer 0 .. L-2, each 1..MT_POLICY_MAX_WIDTH; the last layer has D outputs */
+  int32_t hidden_act;      /* MT_ACT_TANH or MT_ACT_RELU */
+  int32_t out_act;         /* MT_ACT_TANH or MT_ACT_IDENTITY */
+  uint32_t draw;           /* major counter word of the exploration-noise stream */
+  const float* weight[3];  /* DEVICE f32, dense row-major (out, in): torch.nn.Linear.weight as it lies in memory */
+  const float* bias[3];    /* DEVICE f32 (out,) */
+  float out_scale, lo, hi; /* action = clamp(out_scale * out_act(y) + noise, lo, hi) */
+  float sigma[MT_MAX_DOF]; /* per-joint exploration sigma in degrees, finite, >= 0; all zero = deterministic */
+  uint32_t flags;          /* MT_POLICY_* */
+  float* action_log; int64_t act_ld;   /* DEVICE or NULL: (T, D, act_ld), mt_tape's layout: the action handed to step t */
+  float* obs_log;    int64_t obs_ld;   /* DEVICE or NULL: (T, IN, obs_ld): the input vector the policy saw at step t */
+  int8_t* reward_log; uint8_t* done_log; int64_t log_ld; float* return_out;   /* as mt_tape */
+  uint64_t seed;           /* keys the noise stream AND re-armed envs' targets */
+  uint64_t reserved;       /* must be 0 */
+};
+MT_API int mt_rollout_policy(mt_handle h, const struct mt_policy* p);
 
 /* Environment.get_observations(), manytor.py:141-153, at the current pose (also
  * zeroes the coordinates of dead targets, :148).  Result in MT_F_OBS. */

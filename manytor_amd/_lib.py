@@ -206,6 +206,44 @@ MPPI_AUTO_RESET = 0x1
 MPPI_KEEP_MEAN = 0x2
 MPPI_MAX_STEPS = 127
 
+
+class MtPolicy(C.Structure):
+    """struct mt_policy of include/manytor_hip.h: the argument block of mt_rollout_policy."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_steps", C.c_int32),
+        ("n_layers", C.c_int32),
+        ("width", C.c_int32 * 2),
+        ("hidden_act", C.c_int32),
+        ("out_act", C.c_int32),
+        ("draw", C.c_uint32),
+        ("weight", C.c_void_p * 3),
+        ("bias", C.c_void_p * 3),
+        ("out_scale", C.c_float),
+        ("lo", C.c_float),
+        ("hi", C.c_float),
+        ("sigma", C.c_float * MT_MAX_DOF),
+        ("flags", C.c_uint32),
+        ("action_log", C.c_void_p),
+        ("act_ld", C.c_int64),
+        ("obs_log", C.c_void_p),
+        ("obs_ld", C.c_int64),
+        ("reward_log", C.c_void_p),
+        ("done_log", C.c_void_p),
+        ("log_ld", C.c_int64),
+        ("return_out", C.c_void_p),
+        ("seed", C.c_uint64),
+        ("reserved", C.c_uint64),
+    ]
+
+
+POLICY_AUTO_RESET = 0x1
+POLICY_DRY_RUN = 0x2
+POLICY_SEE_POSE = 0x4
+POLICY_MAX_LAYERS = 3
+POLICY_MAX_WIDTH = 64
+ACT_IDENTITY, ACT_TANH, ACT_RELU = 0, 1, 2
+
 _HANDLE = C.c_void_p
 
 # name -> (restype, argtypes); exactly the prototypes of include/manytor_hip.h
@@ -239,6 +277,7 @@ PROTOTYPES = {
     "mt_cem": (C.c_int, [_HANDLE, C.POINTER(MtCem)]),
     "mt_sample_plans": (C.c_int, [_HANDLE, C.POINTER(MtCem), C.c_void_p, C.c_int64, C.c_int64]),
     "mt_mppi": (C.c_int, [_HANDLE, C.POINTER(MtMppi)]),
+    "mt_rollout_policy": (C.c_int, [_HANDLE, C.POINTER(MtPolicy)]),
     "mt_observe": (C.c_int, [_HANDLE]),
     "mt_check_done": (C.c_int, [_HANDLE]),
     "mt_get": (C.c_int, [_HANDLE, C.c_int, C.c_void_p, C.c_int64, C.c_int]),

@@ -311,6 +311,24 @@ class Multienv:
                     [[bool(d) for d in row] for row in done])
         return BatchView(e, L.F_OBS), rew, done
 
+    def run_policy(self, layers, steps, **kw):
+        """`steps` consecutive step()s whose actions an MLP policy computes from each env's observation, in ONE launch
+        (StepEngine.rollout_policy, which documents `layers` and the keywords) -> (obs2 of the LAST step, rewards, dones),
+        shaped by step_sequence's rule."""
+        e = self._engine
+        for name in ("log", "dry_run"):
+            if name in kw:
+                raise TypeError(f"run_policy() sets {name!r} itself")
+        res = e.rollout_policy(layers, steps, log=True, **kw)
+        e.sync()
+        rew = res["reward"].cpu().numpy()
+        done = res["done"].cpu().numpy().astype(bool)
+        self._step_idx += int(rew.shape[0])
+        if self._materialize:
+            return ([row.astype(np.float64) for row in e.obs()], [[int(r) for r in row] for row in rew],
+                    [[bool(d) for d in row] for row in done])
+        return BatchView(e, L.F_OBS), rew, done
+
     def close(self):
         self._engine.close()
 

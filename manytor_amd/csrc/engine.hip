@@ -837,6 +837,25 @@ void launch_tape_select(mt_handle h, const StepArgs& a, const TapeArgs& r) {
   with_table(h, [&](auto tag) { launch_tape_select_t<typename decltype(tag)::type>(h, a, r); });
 }
 
+// rollout_policy_kernel on the whole batch: the tape kernel's shape; W = the smallest compiled extent of the hidden
+// register arrays that holds the policy's widest hidden layer.
+template <class Tbl, int W>
+void launch_policy_t(mt_handle h, const StepArgs& a, const PolicyArgs& r) {
+  const size_t lds = (size_t)3 * h->K * kBlock * sizeof(float);  // 21.5 KB at K = 7, 96 KB at K = 32
+  if (lds > 65536)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_policy_kernel<Tbl, W>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL((rollout_policy_kernel<Tbl, W>), grid_for(a.n), dim3(kBlock), lds, h->stream, a, r);
+}
+void launch_policy(mt_handle h, const StepArgs& a, const PolicyArgs& r, int width) {
+  with_table(h, [&](auto tag) {
+    using Tbl = typename decltype(tag)::type;
+    if (width <= 32) return launch_policy_t<Tbl, 32>(h, a, r);
+    launch_policy_t<Tbl, 64>(h, a, r);
+  });
+}
+
+
 // shoot_kernel on the whole batch: a block per 64 envs, its four waves share the candidates (kernels.h).
 template <class Tbl>
 void launch_shoot_t(mt_handle h, const StepArgs& a, const ShootArgs& r) {
@@ -1415,6 +1434,8 @@ const char* mt_describe_dispatch(mt_handle h) {
       // mt_mppi: cem's shape, every candidate weighted by a power of decay
       ",\"mppi\":{\"usable\":" + b(fusable(h)) + ",\"envs_per_block\":" + num(kShootEnvs) + ",\"waves_per_block\":" + num(kShootWaves) +
       ",\"max_candidates\":64,\"max_steps\":" + num(kMppiMaxSteps) + "}" +
+      // mt_rollout_policy: the tape kernel's shape; hidden vectors in register arrays of one of two compiled extents
+      ",\"policy_rollout\":{\"usable\":" + b(fusable(h)) + ",\"lanes_per_env\":1,\"hidden_extents\":[32,64]}" +
       ",\"reset\":{\"lanes_per_env\":" + num(h->reset_split ? 4 : 1) + "}" +
       // the ground test's interior poses on dense lanes of the block: the step launches that take it (the single-env view,
       // the rollout, tape and shoot kernels never do)
@@ -2201,6 +2222,92 @@ int mt_rollout_tape(mt_handle h, const mt_tape* tape) {
   r.dry_run = dry ? 1u : 0u;
   r.nt_loads = h->tape_nt_loads ? 1u : 0u;
   return commit_tape(h, r, tape->seed, auto_reset, false);
+}
+
+int mt_rollout_policy(mt_handle h, const struct mt_policy* p) {
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  MT_REQUIRE(h, p != nullptr, "policy is NULL");
+  MT_REQUIRE(h, p->struct_size == (int32_t)sizeof(struct mt_policy), "mt_policy.struct_size does not match this library");
+  MT_REQUIRE(h, p->reserved == 0, "mt_policy.reserved must be 0");
+  MT_REQUIRE(h, (p->flags & ~(MT_POLICY_AUTO_RESET | MT_POLICY_DRY_RUN | MT_POLICY_SEE_POSE)) == 0, "mt_policy.flags: unknown MT_POLICY_* flag");
+  const bool auto_reset = (p->flags & MT_POLICY_AUTO_RESET) != 0, dry = (p->flags & MT_POLICY_DRY_RUN) != 0;
+  MT_REQUIRE(h, !(auto_reset && dry), "mt_policy.flags: MT_POLICY_DRY_RUN | MT_POLICY_AUTO_RESET: the re-arm writes the return ring");
+  MT_REQUIRE(h, p->n_steps >= 0 && p->n_steps <= 65535, "mt_policy.n_steps must be 0..65535");
+  const int L = p->n_layers;
+  MT_REQUIRE(h, L >= 1 && L <= MT_POLICY_MAX_LAYERS, "mt_policy.n_layers must be 1.." + std::to_string(MT_POLICY_MAX_LAYERS));
+  int widest = 0;
+  for (int l = 0; l + 1 < L; ++l) {
+    MT_REQUIRE(h, p->width[l] >= 1 && p->width[l] <= MT_POLICY_MAX_WIDTH,
+               "mt_policy.width[" + std::to_string(l) + "] must be 1.." + std::to_string(MT_POLICY_MAX_WIDTH));
+    widest = std::max(widest, (int)p->width[l]);
+  }
+  MT_REQUIRE(h, L == 1 || p->hidden_act == MT_ACT_TANH || p->hidden_act == MT_ACT_RELU, "mt_policy.hidden_act must be MT_ACT_TANH or MT_ACT_RELU");
+  MT_REQUIRE(h, p->out_act == MT_ACT_TANH || p->out_act == MT_ACT_IDENTITY, "mt_policy.out_act must be MT_ACT_TANH or MT_ACT_IDENTITY");
+  // (bit patterns: the build is -ffinite-math-only)
+  MT_REQUIRE(h, first_unusable(&p->lo, 1, kMaxAngleBits) < 0 && first_unusable(&p->hi, 1, kMaxAngleBits) < 0,
+             "mt_policy.lo / hi must be finite and within +-32768 degrees");
+  MT_REQUIRE(h, p->lo <= p->hi, "mt_policy.lo must be <= hi");
+  MT_REQUIRE(h, first_unusable(&p->out_scale, 1, kMaxFiniteBits) < 0, "mt_policy.out_scale must be finite");
+  bool noisy = false;
+  for (int j = 0; j < MT_MAX_DOF; ++j) {
+    MT_REQUIRE(h, first_unusable(&p->sigma[j], 1, kMaxFiniteBits) < 0 && p->sigma[j] >= 0.f,
+               "mt_policy.sigma[" + std::to_string(j) + "] must be finite and >= 0");
+    noisy |= j < h->D && p->sigma[j] > 0.f;
+  }
+  if (!fusable(h)) return fail_unfusable(h, "mt_rollout_policy");
+  if (!h->is_reset) return fail(h, MT_ERR_STATE, "mt_rollout_policy before mt_reset / mt_reset_random");
+  if (p->n_steps == 0) return MT_OK;
+  for (int l = 0; l < L; ++l)
+    MT_REQUIRE(h, p->weight[l] != nullptr && p->bias[l] != nullptr, "mt_policy.weight / bias [" + std::to_string(l) + "] is NULL");
+  MT_REQUIRE(h, !p->action_log || p->act_ld >= h->n, "mt_policy.act_ld is smaller than n_envs");
+  MT_REQUIRE(h, !p->obs_log || p->obs_ld >= h->n, "mt_policy.obs_ld is smaller than n_envs");
+  MT_REQUIRE(h, !(p->reward_log || p->done_log) || p->log_ld >= h->n, "mt_policy.log_ld is smaller than n_envs");
+  MT_ENTER(h);
+  PolicyArgs r{};
+  const bool see_pose = (p->flags & MT_POLICY_SEE_POSE) != 0;
+  int n_in = 3 * h->K + (see_pose ? h->D : 0);
+  for (int l = 0; l < L; ++l) {
+    r.w[l] = p->weight[l];
+    r.b[l] = p->bias[l];
+    r.n_in[l] = n_in;
+    r.n_out[l] = n_in = (l + 1 < L) ? p->width[l] : h->D;
+  }
+  r.L = L;
+  r.T = p->n_steps;
+  r.hidden_act = p->hidden_act;
+  r.out_act = p->out_act;
+  r.out_scale = p->out_scale;
+  r.lo = p->lo;
+  r.hi = p->hi;
+  std::memcpy(r.sigma, p->sigma, sizeof(r.sigma));
+  r.draw = p->draw;
+  r.noisy = noisy ? 1u : 0u;
+  r.see_pose = see_pose ? 1u : 0u;
+  r.action_log = p->action_log;
+  r.act_ld = p->act_ld;
+  r.obs_log = p->obs_log;
+  r.obs_ld = p->obs_ld;
+  r.reward_log = p->reward_log;
+  r.done_log = p->done_log;
+  r.log_ld = p->log_ld;
+  r.return_out = p->return_out;
+  r.auto_reset = auto_reset ? 1u : 0u;
+  r.dry_run = dry ? 1u : 0u;
+  r.seed_lo = (uint32_t)p->seed;
+  r.seed_hi = (uint32_t)(p->seed >> 32);
+  r.radius = h->cfg.radius;
+  if (auto_reset) {  // what commit_tape does ahead of a re-arming launch
+    h->args.seed_lo = (uint32_t)p->seed;
+    h->args.seed_hi = (uint32_t)(p->seed >> 32);
+    int rcg = order_behind_inplace_gather(h, h->stream);
+    if (rcg) return rcg;
+  }
+  launch_policy(h, h->args, r, widest);
+  if (!dry) {
+    h->args.flags &= ~kFlagWholeGoals;  // a policy's angles are anybody's floats
+    h->codes_valid = false;             // the kernel writes targets as floats only
+  }
+  return check_launch(h, "rollout_policy_kernel");
 }
 
 int mt_shoot(mt_handle h, const struct mt_shoot* s) {

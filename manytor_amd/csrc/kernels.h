@@ -2495,6 +2495,340 @@ __global__ __launch_bounds__(kBlock) void rollout_tape_kernel(const StepArgs a, 
 }
 
 // ---------------------------------------------------------------------------
+// rollout driven by an MLP policy (mt_rollout_policy): rollout_tape_kernel with the third action source -- at every step
+// the env's observation at the pose it stands in goes through a small MLP whose output is the action.  State residency,
+// step body, re-arm and write-back are the tape kernel's, on the same lanes (one env per lane, blocks of kBlock), so a
+// call leaves what rollout_tape_kernel leaves for the logged actions, bit for bit.
+//
+// The observation frame of the current pose: after a step it is the `el` route_kinematics returned for the end pose (a
+// held pose included: act == g); at step 0 it is computed as observe_kernel does, and after a re-arm it is the zero
+// pose's, computed once in the prologue.
+//
+// The MLP.  Weights are wave-uniform and are read through the constant address space: scalar loads that feed the FMA's
+// scalar operand, one s_load_dwordx8 per eight v_fmac.  The first layer is accumulated while the observation triples are
+// produced (x is never live as a whole); hidden vectors are register arrays of the compile-time extent W (32 or 64):
+//   first layer  acc[o] += W0[o][k] * x_k for every o of a block of eight outputs that the layer has (wave-uniform skip);
+//                rows past the layer's width read its last row and are zeroed behind the activation
+//   later layers a runtime loop over blocks of eight output rows, each a dot product over the statically indexed input
+//                array in blocks of eight (a block past the layer's inputs is skipped; the one block that straddles them is
+//                read element by element, so no word outside the row is ever loaded, whatever the widths, 1 included);
+//                the eight results enter the output array by ROTATING it by eight, so after W / 8 iterations every
+//                result sits at its own index and no register array is ever indexed dynamically
+// A later layer whose input fills the extent takes a straight-line dot product, the same chain with no wave-uniform branch
+// between the row's scalar loads and its FMAs (the same registers; the same form in the first layer spills SGPRs to
+// scratch for RtTable<8> and is not taken).
+// Accumulation: one fmaf chain per output, inputs in ascending order behind the bias.
+// ---------------------------------------------------------------------------
+struct PolicyArgs {
+  const float* w[3];
+  const float* b[3];
+  int32_t n_in[3], n_out[3];  // per layer; n_in[0] = IN, n_out[L - 1] = D
+  int32_t L, T;
+  int32_t hidden_act, out_act;  // MT_ACT_*
+  float out_scale, lo, hi;
+  float sigma[MT_MAX_DOF];
+  uint32_t draw, noisy, see_pose;
+  float* action_log;  // [T * D][act_ld] or NULL
+  int64_t act_ld;
+  float* obs_log;  // [T * IN][obs_ld] or NULL
+  int64_t obs_ld;
+  int8_t* reward_log;  // as TapeArgs
+  uint8_t* done_log;
+  int64_t log_ld;
+  float* return_out;
+  uint32_t auto_reset, dry_run;
+  uint32_t seed_lo, seed_hi;  // keys the noise stream and the targets of re-armed envs
+  float radius;
+};
+
+using weight_ptr = __attribute__((address_space(4))) const float*;  // constant address space: uniform reads are scalar loads
+__device__ __forceinline__ weight_ptr as_weights(const float* p) { return (weight_ptr)(uint64_t)p; }
+
+// tanh(x) = 1 - 2 / (exp(2 x) + 1): v_exp_f32 and v_rcp_f32 (1 ulp each).  The argument is clamped to +-16 ahead of the
+// multiply and the exponent capped (exp2(44) is finite: the build is -ffinite-math-only, no infinity may be formed, in the
+// product either); at -16 the exponential is 2^-46 and the result is -1 exactly, as tanh is in fp32 from |x| = 9.1 on.
+// A NaN goes through as it is (the clamp would drop it): the action it ends in is then unusable.
+__device__ __forceinline__ bool policy_is_nan(float x) { return (__float_as_uint(x) & 0x7FFFFFFFu) > 0x7F800000u; }
+__device__ __forceinline__ float policy_tanh(float x) {
+  const float xc = fminf(fmaxf(x, -16.f), 16.f);
+  const float e = __builtin_amdgcn_exp2f(fminf(xc * 2.8853900817779268f, 44.f));  // 2 log2(e) x
+  const float t = 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
+  return policy_is_nan(x) ? x : t;
+}
+__device__ __forceinline__ float policy_act(int act, float y) {  // (act is wave-uniform)
+  if (act == MT_ACT_TANH) return policy_tanh(y);
+  if (act == MT_ACT_RELU) return ((__float_as_uint(y) >> 31) && !policy_is_nan(y)) ? 0.f : y;  // a NaN of either sign stays
+  return y;
+}
+
+// acc[o] += W[o][k + q] * x[q], q < NX, for the first layer's outputs o (n_out <= NOUT of them)
+template <int NOUT, int NX>
+__device__ __forceinline__ void policy_feed(float (&acc)[NOUT], weight_ptr w, int n_in, int n_out, int k, const float (&x)[NX]) {
+#pragma unroll
+  for (int o0 = 0; o0 < NOUT; o0 += 8) {
+    if (o0 < n_out) {
+#pragma unroll
+      for (int o = o0; o < o0 + 8 && o < NOUT; ++o) {
+        const weight_ptr row = w + (int64_t)min(o, n_out - 1) * n_in + k;
+#pragma unroll
+        for (int q = 0; q < NX; ++q) acc[o] = __builtin_fmaf(row[q], x[q], acc[o]);
+      }
+    }
+  }
+}
+// the first layer's accumulators before the first input: the bias
+template <int NOUT>
+__device__ __forceinline__ void policy_bias(float (&acc)[NOUT], weight_ptr b, int n_out) {
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) acc[o] = b[min(o, n_out - 1)];
+}
+// ... and behind the last one: the activation, zeros past the layer's width
+template <int NOUT>
+__device__ __forceinline__ void policy_finish(float (&acc)[NOUT], int act, int n_out) {
+#pragma unroll
+  for (int o = 0; o < NOUT; ++o) acc[o] = o < n_out ? policy_act(act, acc[o]) : 0.f;
+}
+// b + W[row][0 .. n_in) . h: whole blocks of eight as they are, the block that straddles n_in element by element
+template <int W>
+__device__ __forceinline__ float policy_dot(weight_ptr row, float bias, int n_in, const float (&h)[W]) {
+  float acc = bias;
+  if (n_in == W) {  // a full row: straight-line, no wave-uniform branch between the row's scalar loads and its FMAs
+#pragma unroll
+    for (int k = 0; k < W; ++k) acc = __builtin_fmaf(row[k], h[k], acc);
+    return acc;
+  }
+#pragma unroll
+  for (int k0 = 0; k0 < W; k0 += 8) {
+    if (k0 + 8 <= n_in) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) acc = __builtin_fmaf(row[k0 + q], h[k0 + q], acc);
+    } else if (k0 < n_in) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q)
+        if (k0 + q < n_in) acc = __builtin_fmaf(row[k0 + q], h[k0 + q], acc);
+    }
+  }
+  return acc;
+}
+// a hidden layer behind the first: out = act(W in + b), n_out <= W outputs, zeros past them
+template <int W>
+__device__ __forceinline__ void policy_hidden(weight_ptr w, weight_ptr b, int n_in, int n_out, int act, const float (&in)[W],
+                                              float (&out)[W]) {
+#pragma unroll 1
+  for (int o0 = 0; o0 < W; o0 += 8) {
+    float v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int o = o0 + q;
+      v[q] = 0.f;
+      if (o < n_out) v[q] = policy_act(act, policy_dot<W>(w + (int64_t)o * n_in, b[o], n_in, in));
+    }
+#pragma unroll
+    for (int o = 0; o < W - 8; ++o) out[o] = out[o + 8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) out[W - 8 + q] = v[q];
+  }
+}
+
+// the observation frame's origin at pose g, as observe_kernel computes it
+template <int D>
+__device__ __forceinline__ void pose_obs_frame(const DhConst& dh, const float (&g)[D], float (&el)[3]) {
+  float s[D], c[D], p[D][3], e_unused[3];
+#pragma unroll
+  for (int j = 0; j < D; ++j) sincos_deg_off(g[j], dh.off_deg[j], s[j], c[j]);
+  const RtTableF<D> t{dh};
+  chain_all<RtTableF<D>>(s, c, t, p);
+  pick_frames<RtTableF<D>>(t, p, el, e_unused);
+}
+
+template <class Tbl, int W>
+__global__ __launch_bounds__(kBlock) void rollout_policy_kernel(const StepArgs a, const PolicyArgs r) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];  // [3K][kBlock]
+  constexpr int D = Tbl::D;
+  const Tbl t = TableMaker<Tbl>::make(a.dh);
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  LaneOffset<true> o4{i * 4u}, o1{i};
+  if (i >= a.n) return;  // (no block barrier and no wave-cooperative draw below)
+  const int64_t ld = a.ld;
+  const uint64_t seed = ((uint64_t)r.seed_hi << 32) | r.seed_lo;
+  const uint64_t env_id = (uint64_t)(a.env_base + i);
+  const TargetColumn<kBlock> tc{tile + threadIdx.x};
+  const bool commit = r.dry_run == 0;  // (wave-uniform: a launch argument)
+  const int L = r.L, IN = r.n_in[0];
+  const weight_ptr w0 = as_weights(r.w[0]), b0 = as_weights(r.b[0]);
+  const weight_ptr wl = as_weights(r.w[L - 1]), bl = as_weights(r.b[L - 1]);  // the output layer (the first one when L == 1)
+
+  const uint32_t all_alive = all_alive_mask(a.K);
+  float g[D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) g[j] = ldr(a.goals + j * ld, o4);
+  uint32_t am = ldr(a.alive, o4);
+  float total = ldr(a.total_reward, o4);
+  uint32_t episode = r.auto_reset ? ldr(a.episodes, o4) : 0u;
+  for (int k = 0; k < 3 * a.K; ++k) tc.row(k) = ldr(a.points + (int64_t)k * ld, o4);
+  bool ended = false, dirty = false;
+  float ret = 0.f;  // sum of this call's rewards, across re-arms
+  PoseCache<D> pose;
+  bool pose_valid = false;  // nothing known about the pose loaded from memory
+  float el_cur[3], el_zero[3] = {0.f, 0.f, 0.f};
+  pose_obs_frame<D>(a.dh, g, el_cur);
+  if (r.auto_reset) {
+    float zero[D];
+#pragma unroll
+    for (int j = 0; j < D; ++j) zero[j] = 0.f;
+    pose_obs_frame<D>(a.dh, zero, el_zero);
+  }
+
+  // the policy's input at the state the step starts from, streamed into the first layer's accumulators
+  auto first_layer = [&](auto& acc, int n_out, int s) {
+    policy_bias(acc, b0, n_out);
+    for (int k = 0; k < a.K; ++k) {
+      float x, y, z, tri[3] = {0.f, 0.f, 0.f};
+      tc.get(k, x, y, z);
+      if ((am >> k) & 1u) observe_target(el_cur, x, y, z, tri[0], tri[1], tri[2]);
+      if (r.obs_log) {
+        float* orow = r.obs_log + ((int64_t)s * IN + 3 * k) * r.obs_ld;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) str_stream(orow + q * r.obs_ld, o4, tri[q]);
+      }
+      policy_feed(acc, w0, IN, n_out, 3 * k, tri);
+    }
+    if (r.see_pose) {
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        if (r.obs_log) str_stream(r.obs_log + ((int64_t)s * IN + 3 * a.K + j) * r.obs_ld, o4, g[j]);
+        const float xj[1] = {g[j]};
+        policy_feed(acc, w0, IN, n_out, 3 * a.K + j, xj);
+      }
+    }
+  };
+
+  for (int s = 0; s < r.T; ++s) {
+    const bool last = s == r.T - 1;  // (wave-uniform)
+    float act[D], raw[D], el[3], e[3];
+    {  // observe -> MLP -> raw action
+      float y[D];
+      if (L == 1) {
+        first_layer(y, D, s);
+      } else {
+        float h0[W];
+        first_layer(h0, r.n_out[0], s);
+        policy_finish(h0, r.hidden_act, r.n_out[0]);
+        if (L == 2) {
+#pragma unroll
+          for (int j = 0; j < D; ++j) y[j] = policy_dot<W>(wl + (int64_t)j * r.n_in[1], bl[j], r.n_in[1], h0);
+        } else {
+          float h1[W];
+#pragma unroll
+          for (int o = 0; o < W; ++o) h1[o] = 0.f;
+          policy_hidden<W>(as_weights(r.w[1]), as_weights(r.b[1]), r.n_in[1], r.n_out[1], r.hidden_act, h0, h1);
+#pragma unroll
+          for (int j = 0; j < D; ++j) y[j] = policy_dot<W>(wl + (int64_t)j * r.n_in[2], bl[j], r.n_in[2], h1);
+        }
+      }
+      uint32_t nw[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+      if (r.noisy) {
+        const u32x4 n0 = stream_block(seed, env_id, kTagPolicy, r.draw, plan_minor(0u, 0u, (uint32_t)s));
+        nw[0] = n0.x, nw[1] = n0.y, nw[2] = n0.z, nw[3] = n0.w;
+        if constexpr (D > 4) {
+          const u32x4 n1 = stream_block(seed, env_id, kTagPolicy, r.draw, plan_minor(0u, 1u, (uint32_t)s));
+          nw[4] = n1.x, nw[5] = n1.y, nw[6] = n1.z, nw[7] = n1.w;
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        float v = r.out_scale * policy_act(r.out_act, y[j]);
+        if (r.noisy && r.sigma[j] > 0.f) {
+          const float sz = r.sigma[j] * plan_noise(nw[j]);
+          v = v + sz;
+        }
+        raw[j] = unusable_angle(v) ? v : fminf(fmaxf(v, r.lo), r.hi);
+        if (r.action_log) str_stream(r.action_log + ((int64_t)s * D + j) * r.act_ld, o4, raw[j]);
+      }
+    }
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < D; ++j) bad |= unusable_angle(raw[j]);
+#pragma unroll
+    for (int j = 0; j < D; ++j) act[j] = bad ? g[j] : raw[j];  // the env holds its pose this step
+    if (bad && commit) atomicAdd(a.bad_actions, 1u);          // ... and the pair is counted (mt_bad_action_count)
+
+    const float zmin = route_kinematics<Tbl, 0, true, false>(t, a.S, a.inv_sm1, g, act, el, e, &pose, pose_valid, nullptr, false);
+    pose_valid = true;
+    const bool ground = zmin < 0.f;
+    const bool out = last && commit;  // the step whose outputs MT_F_* keep
+    if (out && a.zmin) str_stream(a.zmin, o4, zmin);
+
+    uint32_t nam = am;
+    for (int k = 0; k < a.K; ++k) {
+      float x, y, z, dist = 0.f, rr = 0.f, th = 0.f;
+      tc.get(k, x, y, z);
+      if ((am >> k) & 1u) {
+        if (out) observe_target(el, x, y, z, dist, rr, th);
+        if (within_box(e, x, y, z, a.tol)) nam &= ~(1u << k);
+      } else if ((x != 0.f) | (y != 0.f) | (z != 0.f)) {  // manytor.py:148
+        tc.zero(k);
+        dirty = true;
+      }
+      if (out) {
+        float* orow = a.obs + (int64_t)(3 * k) * ld;
+        str_stream(orow, o4, dist);
+        str_stream(orow + ld, o4, rr);
+        str_stream(orow + 2 * ld, o4, th);
+      }
+    }
+    const int32_t rew = ground ? -1 : ((nam != am) ? 1 : 0);
+    bool done = (nam == 0u);
+    if (a.flags & MT_FLAG_TERMINATE_ON_GROUND) done |= ground;
+    total += (float)rew;
+    ret += (float)rew;
+    am = nam;
+#pragma unroll
+    for (int j = 0; j < D; ++j) g[j] = act[j];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) el_cur[q] = el[q];
+    if (r.reward_log) str_stream(r.reward_log + (int64_t)s * r.log_ld, o1, (int8_t)rew);
+    if (r.done_log) str_stream(r.done_log + (int64_t)s * r.log_ld, o1, (uint8_t)(done ? 1 : 0));
+    if (out) {
+#pragma unroll
+      for (int j = 0; j < D; ++j) str(a.actions + j * ld, o4, raw[j]);  // what mt_set_actions(row T - 1) would have left
+#pragma unroll
+      for (int q = 0; q < 3; ++q) str_stream(a.ee + q * ld, o4, e[q]);
+      str_stream(a.reward, o4, rew);
+      // 2 = "finished in this step and already re-armed below" (see rollout_kernel)
+      str_stream(a.done, o1, (uint8_t)(done ? (r.auto_reset ? 2 : 1) : 0));
+      const unsigned long long bits = __ballot(done);
+      if ((threadIdx.x & 63) == 0) a.done_bits[i >> 6] = bits;
+    }
+
+    if (done && r.auto_reset) {  // re-arm, as in rollout_kernel (never in a dry run: the host refuses the combination)
+      record_finished(a, i, episode, total);
+      ended = true;
+      total = 0.f;
+      am = all_alive;
+      episode += 1u;
+#pragma unroll
+      for (int j = 0; j < D; ++j) g[j] = 0.f;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) el_cur[q] = el_zero[q];
+      pose_valid = false;
+      draw_targets(seed, env_id, episode, a.K, r.radius, [&](int k, float x, float y, float z) { tc.put(k, x, y, z); });
+      dirty = true;
+    }
+  }
+
+  if (r.return_out) str_stream(r.return_out, o4, ret);
+  if (!commit) return;
+#pragma unroll
+  for (int j = 0; j < D; ++j) str(a.goals + j * ld, o4, g[j]);
+  str(a.alive, o4, am);
+  str(a.total_reward, o4, total);
+  if (ended) str(a.episodes, o4, episode);
+  if (dirty)
+    for (int k = 0; k < 3 * a.K; ++k) str(a.points + (int64_t)k * ld, o4, tc.row(k));
+}
+
+// ---------------------------------------------------------------------------
 // mt_shoot's evaluation: C candidate tapes per env scored from the SAME resident state, the best one named.  For env i
 // and candidate c, returns[c][i] is what rollout_tape_kernel's dry run writes to return_out[i] for plane c, bit for bit;
 // best[i] is the smallest c whose return is maximal.  Nothing resident is written.

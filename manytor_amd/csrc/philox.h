@@ -16,6 +16,7 @@ namespace mt {
 constexpr uint32_t kTagAction = 1u;
 constexpr uint32_t kTagTarget = 2u;
 constexpr uint32_t kTagPlan = 3u;  // mt_cem / mt_sample_plans: the noise of candidate plans
+constexpr uint32_t kTagPolicy = 4u;  // mt_rollout_policy: the exploration noise of a policy's actions
 
 struct u32x4 {
   uint32_t x, y, z, w;

@@ -512,6 +512,112 @@ class StepEngine:
         self._torch_call(self._lib.mt_rollout_tape, C.byref(arg), commits=not dry_run)
         return out or None
 
+    _ACTIVATIONS = {"identity": L.ACT_IDENTITY, "tanh": L.ACT_TANH, "relu": L.ACT_RELU}
+
+    @staticmethod
+    def _policy_layers(layers, hidden, out):
+        """[(weight, bias), ...] of a policy given as such a list or as a torch.nn.Sequential of Linear / Tanh / ReLU, whose
+        activations must then be the one `hidden` and the one `out` of the call."""
+        import torch
+        if not isinstance(layers, torch.nn.Sequential):
+            return [tuple(pair) for pair in layers]
+        names = {torch.nn.Tanh: "tanh", torch.nn.ReLU: "relu"}
+        pairs, acts = [], []
+        for m in layers:
+            if isinstance(m, torch.nn.Linear):
+                if m.bias is None:
+                    raise ValueError(f"layer {len(pairs)}: a Linear without bias is not supported")
+                pairs.append((m.weight, m.bias))
+                acts.append("identity")
+            elif type(m) in names and pairs and acts[-1] == "identity":
+                acts[-1] = names[type(m)]
+            else:
+                raise ValueError(f"a policy module is Linear layers, each followed by at most one Tanh or ReLU; got {type(m).__name__}")
+        if not pairs:
+            raise ValueError("the policy has no Linear layer")
+        if any(a != hidden for a in acts[:-1]) or acts[-1] != out:
+            raise ValueError(f"the module's activations {acts} do not agree with hidden={hidden!r}, out={out!r}")
+        return pairs
+
+    def rollout_policy(self, layers, steps, *, hidden="tanh", out="tanh", out_scale=180.0, see_pose=False, sigma=None, draw=0,
+                       seed=0x5EED, auto_reset=False, lo=-180., hi=180., log=False, returns=False, actions=False,
+                       observations=False, dry_run=False):
+        """`steps` steps driven by an MLP policy in ONE launch (mt_rollout_policy): at every step each env's observation at
+        the state it is in (the 3K floats observe() would give; see_pose=True appends the D joint angles) goes through
+        `layers` -- a list of (weight, bias) CUDA float32 tensors in torch.nn.Linear layout, read in place, or a
+        torch.nn.Sequential of Linear / Tanh / ReLU -- and action = clamp(out_scale * out(y) + sigma * z, lo, hi) is
+        stepped.  At most 3 layers, hidden widths up to 64; hidden in ("tanh", "relu"), out in ("tanh", "identity").
+        sigma: None, a float or D floats (degrees): exploration noise from the (seed, env, draw, step) stream.  The
+        state afterwards is what rollout_actions leaves for the logged actions.  Returns a dict of device tensors (None
+        when nothing is asked for): log -> `reward` (T, N) int8, `done` (T, N) uint8; returns -> `returns` (N,);
+        actions -> `actions` (T, D, N); observations -> `observations` (T, IN, N).  dry_run=True evaluates only.
+        Stream behaviour as rollout_actions."""
+        import torch
+        if auto_reset and dry_run:
+            raise ValueError("dry_run and auto_reset exclude each other: the re-arm writes the return ring")
+        for name, v, allowed in (("hidden", hidden, ("tanh", "relu")), ("out", out, ("tanh", "identity"))):
+            if v not in allowed:
+                raise ValueError(f"{name} must be one of {allowed}, got {v!r}")
+        pairs = self._policy_layers(layers, hidden, out)
+        if not 1 <= len(pairs) <= L.POLICY_MAX_LAYERS:
+            raise ValueError(f"a policy has 1..{L.POLICY_MAX_LAYERS} linear layers, got {len(pairs)}")
+        T, n, d = int(steps), self.n_envs, self.dof
+        if not 0 <= T <= 65535:
+            raise ValueError(f"steps must be 0..65535, got {T}")
+        dev = torch.device("cuda", self.device)
+        n_in = 3 * self.obj_number + (d if see_pose else 0)
+        arg = L.MtPolicy()
+        keep = []
+        fan_in = n_in
+        for l, (w, b) in enumerate(pairs):
+            w, b = w.detach(), b.detach()
+            fan_out = d if l == len(pairs) - 1 else int(w.shape[0]) if w.dim() == 2 else -1
+            if tuple(w.shape) != (fan_out, fan_in) or tuple(b.shape) != (fan_out,):
+                raise ValueError(f"layer {l}: weight must be ({fan_out if fan_out > 0 else 'out'}, {fan_in}) and bias (out,), got "
+                                 f"{tuple(w.shape)} and {tuple(b.shape)}")
+            if l < len(pairs) - 1 and not 1 <= fan_out <= L.POLICY_MAX_WIDTH:
+                raise ValueError(f"layer {l}: width must be 1..{L.POLICY_MAX_WIDTH}, got {fan_out}")
+            for what, t in (("weight", w), ("bias", b)):
+                if t.dtype != torch.float32 or not t.is_cuda or t.device != dev or not t.is_contiguous():
+                    raise ValueError(f"layer {l}: {what} must be a contiguous float32 tensor on {dev}")
+            keep += [w, b]
+            arg.weight[l], arg.bias[l] = w.data_ptr(), b.data_ptr()
+            if l < len(pairs) - 1:
+                arg.width[l] = fan_out
+            fan_in = fan_out
+        sig = np.zeros(L.MT_MAX_DOF, dtype=np.float32)
+        if sigma is not None:
+            sig[:d] = np.broadcast_to(np.asarray(sigma, dtype=np.float32), (d,))
+        res = {}
+        if log:
+            res["reward"] = torch.empty((T, n), dtype=torch.int8, device=dev)
+            res["done"] = torch.empty((T, n), dtype=torch.uint8, device=dev)
+        if returns:
+            res["returns"] = torch.zeros(n, dtype=torch.float32, device=dev)
+        if actions:
+            res["actions"] = torch.empty((T, d, n), dtype=torch.float32, device=dev)
+        if observations:
+            res["observations"] = torch.empty((T, n_in, n), dtype=torch.float32, device=dev)
+        arg.struct_size = C.sizeof(L.MtPolicy)
+        arg.n_steps, arg.n_layers = T, len(pairs)
+        arg.hidden_act, arg.out_act = self._ACTIVATIONS[hidden], self._ACTIVATIONS[out]
+        arg.draw = int(draw) & 0xFFFFFFFF
+        arg.out_scale, arg.lo, arg.hi = float(out_scale), float(lo), float(hi)
+        arg.sigma[:] = sig.tolist()
+        arg.flags = ((L.POLICY_AUTO_RESET if auto_reset else 0) | (L.POLICY_DRY_RUN if dry_run else 0)
+                     | (L.POLICY_SEE_POSE if see_pose else 0))
+        arg.action_log = res["actions"].data_ptr() if actions and T else None
+        arg.obs_log = res["observations"].data_ptr() if observations and T else None
+        arg.reward_log = res["reward"].data_ptr() if log and T else None
+        arg.done_log = res["done"].data_ptr() if log and T else None
+        arg.act_ld = arg.obs_ld = arg.log_ld = n
+        arg.return_out = res["returns"].data_ptr() if returns else None
+        arg.seed = int(seed)
+        arg.reserved = 0
+        self._torch_call(self._lib.mt_rollout_policy, C.byref(arg), commits=not dry_run)
+        del keep
+        return res or None
+
     def shoot(self, plans, *, layout="soa", commit=0, auto_reset=False, seed=0x5EED, all_returns=False, log=False,
               returns=False):
         """A sampling planner's round in one call (mt_shoot): `plans` holds C candidate tapes of T steps per env, (C, T, D, N)
