@@ -40,7 +40,7 @@ extern "C" {
 #define MT_API
 #endif
 
-#define MT_VERSION 440          /* major*10000 + minor*100 + patch */
+#define MT_VERSION 450         /* major*10000 + minor*100 + patch */
 #define MT_MAX_DOF 8
 #define MT_MAX_TARGETS 32
 #define MT_MAX_RETURN_RING 64
@@ -475,6 +475,99 @@ struct mt_policy {         /* as with mt_cem, the type is always written `struct
   uint64_t reserved;       /* must be 0 */
 };
 MT_API int mt_rollout_policy(mt_handle h, const struct mt_policy* p);
+
+/* An evolution-strategies generation: the planners' three levels (mt_sample_plans; mt_shoot; mt_cem / mt_mppi) in
+ * PARAMETER space -- mt_es_sample perturbs, mt_rollout_population scores, mt_es runs the generation in one call.
+ *
+ * Population shape.  M members, M even, 2 <= M <= MT_ES_MAX_MEMBERS.  Member m owns the G = n_envs / M consecutive envs
+ * [mG, (m+1)G) of the handle; G must be a multiple of 256, the rollout block, so that every block, and with it every
+ * wave, belongs to one member and the weights stay wave-uniform scalar operands.  Anything else is MT_ERR_INVALID_ARG.
+ * Flat parameters.  theta is P floats, W0 (n_out0 x IN) | b0 | W1 | b1 | W2 | b2, each W dense row-major (out, in): what
+ * struct mt_policy's weight[l] / bias[l] point at, laid end to end.  IN, the widths, L, the activations, out_scale, lo, hi
+ * and MT_POLICY_SEE_POSE are those of mt_rollout_policy.  A population is (M, pitch) f32 in DEVICE memory, pitch >= P,
+ * the caller's workspace: no call allocates.
+ * Perturbation (mt_es_sample).  Pair p = m >> 1, sign + for even m and - for odd m (antithetic).  eps(p, i) is the
+ * Irwin-Hall variate of mt_cem -- (byte sum - 510) * KZ -- of word i & 3 of the Philox-4x32-10 block with counter
+ * (p, 5 << 24, draw, i >> 2), key = seed: tag 5, the pair in the env's place.  pop[m][i] = theta[i] +- (sigma * eps): one
+ * fp32 multiply, then one fp32 add or subtract, not fused.  sigma is one finite positive float.  One launch; words
+ * [P, pitch) of a row are not written.
+ * Scoring (mt_rollout_population).  mt_rollout_policy with one change: a block reads its member's weights, every weight
+ * and bias pointer advanced by m * pitch.  No action noise (ES explores in parameter space).  The flags
+ * (MT_POLICY_AUTO_RESET, _DRY_RUN, _SEE_POSE), the logs, return_out, the commit semantics, the refusals and legality
+ * under capture are mt_rollout_policy's: env i of member m gets, bit for bit, what mt_rollout_policy gives env i with row
+ * m as the weights.  fitness_out (needs return_out) adds one small launch: fitness[m] as defined below.
+ * Update (mt_es): sample -> score -> update on the handle's stream, four launches, no host wait, no allocation.  The
+ * caller supplies theta, the population, a (n_envs,) f32 return row (pop.return_out) and (M / 2 + M,) int64 words for
+ * the coefficients and the sums; all are left filled.  R_i, the call's return of env i, is an integer-valued float, |R_i| <= 127 T < 2^24.
+ *   S_m        = sum of R_i over member m, in int64 (the order is free)
+ *   fitness[m] = (float)S_m * inv_G, inv_G the fp32 nearest to 1 / G: one conversion, one multiply
+ *   best       = the lowest m with the largest S_m
+ *   c_m        = MT_ES_SHAPE_RANK: 2 #{j : S_j < S_m} + #{j != m : S_j == S_m} (centred mid-ranks: ties favour neither
+ *                half of a pair);  MT_ES_SHAPE_RAW: S_m.  A baseline cancels in an antithetic difference: none is taken.
+ *   coeff[p]   = c_2p - c_2p+1
+ *   A_i        = sum over p of coeff[p] * (bytesum(p, i) - 510), in int64
+ *   grad[i]    = (float)A_i * scale, scale the fp32 nearest to the double KZ / (M sigma 2(M-1)) (rank) or
+ *                KZ / (M sigma G) (raw), from the fp32 KZ and the fp32 sigma
+ * The noise is regenerated from Philox: no (M, P) noise tensor exists.  grad_out is always written; with MT_ES_INPLACE
+ * theta[i] += lr * grad[i], a multiply, then an add.  MT_ES_UPDATE_ONLY skips sample and score and takes pop.return_out as
+ * the caller filled it (integer-valued, |R_i| <= 127 T): the update of returns shaped or gathered elsewhere.  The host
+ * refuses M, G and T with which A_i could leave int64.  n_steps == 0 is a no-op. */
+#define MT_ES_MAX_MEMBERS 4096
+#define MT_ES_INPLACE     0x1u
+#define MT_ES_UPDATE_ONLY 0x2u
+enum { MT_ES_SHAPE_RANK = 0, MT_ES_SHAPE_RAW = 1 };
+struct mt_es_sample {      /* as with mt_cem, the type is always written `struct mt_es_sample` */
+  int32_t struct_size;     /* = sizeof(struct mt_es_sample), checked */
+  int32_t n_members;       /* M */
+  int64_t n_params;        /* P, 1..2^31 */
+  const float* theta;      /* DEVICE f32 (P,) */
+  float* pop;              /* DEVICE f32 (M, pitch): written; must not overlap theta */
+  int64_t pitch;           /* floats between rows, >= P */
+  float sigma;             /* finite, > 0 */
+  uint32_t draw;           /* major counter word of the parameter-noise stream */
+  uint64_t seed;
+  uint64_t reserved;       /* must be 0 */
+};
+MT_API int mt_es_sample(mt_handle h, const struct mt_es_sample* s);
+
+struct mt_population {     /* mt_policy with the weights taken from a population's rows, without sigma / draw */
+  int32_t struct_size;     /* = sizeof(struct mt_population), checked */
+  int32_t n_steps;         /* T, 0..65535 */
+  int32_t n_members;       /* M */
+  int32_t n_layers;        /* L, as mt_policy */
+  int32_t width[2];
+  int32_t hidden_act;
+  int32_t out_act;
+  const float* pop;        /* DEVICE f32 (M, pitch) */
+  int64_t pitch;           /* >= P of the policy's shape */
+  float out_scale, lo, hi;
+  uint32_t flags;          /* MT_POLICY_* */
+  float* action_log; int64_t act_ld;
+  float* obs_log;    int64_t obs_ld;
+  int8_t* reward_log; uint8_t* done_log; int64_t log_ld; float* return_out;   /* as mt_policy */
+  float* fitness_out;      /* DEVICE or NULL: (M,) */
+  uint64_t seed;           /* keys re-armed envs' targets */
+  uint64_t reserved;       /* must be 0 */
+};
+MT_API int mt_rollout_population(mt_handle h, const struct mt_population* p);
+
+struct mt_es {
+  int32_t struct_size;     /* = sizeof(struct mt_es), checked */
+  int32_t shaping;         /* MT_ES_SHAPE_* */
+  float sigma;             /* finite, > 0 */
+  float lr;                /* finite; read with MT_ES_INPLACE */
+  uint32_t draw;
+  uint32_t flags;          /* MT_ES_* */
+  float* theta;            /* DEVICE f32 (P,): read; updated with MT_ES_INPLACE */
+  float* grad_out;         /* DEVICE f32 (P,): always written */
+  int32_t* best_out;       /* DEVICE or NULL: (1,) */
+  int64_t* coeff_out;      /* DEVICE int64 (M / 2 + M,): workspace, left holding coeff[p], p < M / 2, then S_m, m < M */
+  struct mt_population pop; /* the scoring: pop.pop is the (M, pitch) workspace the sample writes, pop.return_out the
+                              (n_envs,) return row (both required), pop.fitness_out the fitness; pop.seed keys the
+                              parameter noise as well */
+  uint64_t reserved;       /* must be 0 */
+};
+MT_API int mt_es(mt_handle h, const struct mt_es* s);
 
 /* Environment.get_observations(), manytor.py:141-153, at the current pose (also
  * zeroes the coordinates of dead targets, :148).  Result in MT_F_OBS. */

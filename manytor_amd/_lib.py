@@ -244,6 +244,76 @@ POLICY_MAX_LAYERS = 3
 POLICY_MAX_WIDTH = 64
 ACT_IDENTITY, ACT_TANH, ACT_RELU = 0, 1, 2
 
+
+class MtEsSample(C.Structure):
+    """struct mt_es_sample of include/manytor_hip.h: the argument block of mt_es_sample."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_members", C.c_int32),
+        ("n_params", C.c_int64),
+        ("theta", C.c_void_p),
+        ("pop", C.c_void_p),
+        ("pitch", C.c_int64),
+        ("sigma", C.c_float),
+        ("draw", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("reserved", C.c_uint64),
+    ]
+
+
+class MtPopulation(C.Structure):
+    """struct mt_population: the argument block of mt_rollout_population, and mt_es's scoring."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_steps", C.c_int32),
+        ("n_members", C.c_int32),
+        ("n_layers", C.c_int32),
+        ("width", C.c_int32 * 2),
+        ("hidden_act", C.c_int32),
+        ("out_act", C.c_int32),
+        ("pop", C.c_void_p),
+        ("pitch", C.c_int64),
+        ("out_scale", C.c_float),
+        ("lo", C.c_float),
+        ("hi", C.c_float),
+        ("flags", C.c_uint32),
+        ("action_log", C.c_void_p),
+        ("act_ld", C.c_int64),
+        ("obs_log", C.c_void_p),
+        ("obs_ld", C.c_int64),
+        ("reward_log", C.c_void_p),
+        ("done_log", C.c_void_p),
+        ("log_ld", C.c_int64),
+        ("return_out", C.c_void_p),
+        ("fitness_out", C.c_void_p),
+        ("seed", C.c_uint64),
+        ("reserved", C.c_uint64),
+    ]
+
+
+class MtEs(C.Structure):
+    """struct mt_es: the argument block of mt_es."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("shaping", C.c_int32),
+        ("sigma", C.c_float),
+        ("lr", C.c_float),
+        ("draw", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("theta", C.c_void_p),
+        ("grad_out", C.c_void_p),
+        ("best_out", C.c_void_p),
+        ("coeff_out", C.c_void_p),
+        ("pop", MtPopulation),
+        ("reserved", C.c_uint64),
+    ]
+
+
+ES_MAX_MEMBERS = 4096
+ES_INPLACE = 0x1
+ES_UPDATE_ONLY = 0x2
+ES_SHAPE_RANK, ES_SHAPE_RAW = 0, 1
+
 _HANDLE = C.c_void_p
 
 # name -> (restype, argtypes); exactly the prototypes of include/manytor_hip.h
@@ -278,6 +348,9 @@ PROTOTYPES = {
     "mt_sample_plans": (C.c_int, [_HANDLE, C.POINTER(MtCem), C.c_void_p, C.c_int64, C.c_int64]),
     "mt_mppi": (C.c_int, [_HANDLE, C.POINTER(MtMppi)]),
     "mt_rollout_policy": (C.c_int, [_HANDLE, C.POINTER(MtPolicy)]),
+    "mt_es_sample": (C.c_int, [_HANDLE, C.POINTER(MtEsSample)]),
+    "mt_rollout_population": (C.c_int, [_HANDLE, C.POINTER(MtPopulation)]),
+    "mt_es": (C.c_int, [_HANDLE, C.POINTER(MtEs)]),
     "mt_observe": (C.c_int, [_HANDLE]),
     "mt_check_done": (C.c_int, [_HANDLE]),
     "mt_get": (C.c_int, [_HANDLE, C.c_int, C.c_void_p, C.c_int64, C.c_int]),

@@ -329,6 +329,17 @@ class Multienv:
                     [[bool(d) for d in row] for row in done])
         return BatchView(e, L.F_OBS), rew, done
 
+    def evolve_policy(self, theta, sigma, members, steps, **kw):
+        """One evolution-strategies generation on the batch in one call (StepEngine.es, which documents the keywords):
+        `members` antithetic perturbations of the flat policy parameters `theta`, each scored on its own n_envs / members
+        envs over `steps` step()s -> StepEngine.es's dict of device tensors (`grad`, `fitness`, `best`, `returns`,
+        `population`).  The envs move as under run_policy unless dry_run=True."""
+        e = self._engine
+        res = e.es(theta, sigma, members=members, steps=steps, **kw)
+        if not kw.get("dry_run") and not kw.get("update_only"):
+            self._step_idx += int(steps)
+        return res
+
     def close(self):
         self._engine.close()
 

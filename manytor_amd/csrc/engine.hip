@@ -2224,45 +2224,57 @@ int mt_rollout_tape(mt_handle h, const mt_tape* tape) {
   return commit_tape(h, r, tape->seed, auto_reset, false);
 }
 
-int mt_rollout_policy(mt_handle h, const struct mt_policy* p) {
-  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
-  MT_REQUIRE(h, p != nullptr, "policy is NULL");
-  MT_REQUIRE(h, p->struct_size == (int32_t)sizeof(struct mt_policy), "mt_policy.struct_size does not match this library");
-  MT_REQUIRE(h, p->reserved == 0, "mt_policy.reserved must be 0");
-  MT_REQUIRE(h, (p->flags & ~(MT_POLICY_AUTO_RESET | MT_POLICY_DRY_RUN | MT_POLICY_SEE_POSE)) == 0, "mt_policy.flags: unknown MT_POLICY_* flag");
+// mt_rollout_policy, and mt_rollout_population with member 0's rows as the weights, in two halves: everything the host can
+// refuse (`nm` is the struct the messages name, `who` the entry point), which launches nothing and changes nothing, and
+// the launch.  A call with n_steps == 0 passes the screen and is the caller's no-op.
+struct PolicyScreen {
+  int widest = 0;
+  bool noisy = false;
+};
+static int rollout_policy_screen(mt_handle h, const struct mt_policy* p, const std::string& nm, const char* who, PolicyScreen* out) {
+  MT_REQUIRE(h, (p->flags & ~(MT_POLICY_AUTO_RESET | MT_POLICY_DRY_RUN | MT_POLICY_SEE_POSE)) == 0, nm + ".flags: unknown MT_POLICY_* flag");
   const bool auto_reset = (p->flags & MT_POLICY_AUTO_RESET) != 0, dry = (p->flags & MT_POLICY_DRY_RUN) != 0;
-  MT_REQUIRE(h, !(auto_reset && dry), "mt_policy.flags: MT_POLICY_DRY_RUN | MT_POLICY_AUTO_RESET: the re-arm writes the return ring");
-  MT_REQUIRE(h, p->n_steps >= 0 && p->n_steps <= 65535, "mt_policy.n_steps must be 0..65535");
+  MT_REQUIRE(h, !(auto_reset && dry), nm + ".flags: MT_POLICY_DRY_RUN | MT_POLICY_AUTO_RESET: the re-arm writes the return ring");
+  MT_REQUIRE(h, p->n_steps >= 0 && p->n_steps <= 65535, nm + ".n_steps must be 0..65535");
   const int L = p->n_layers;
-  MT_REQUIRE(h, L >= 1 && L <= MT_POLICY_MAX_LAYERS, "mt_policy.n_layers must be 1.." + std::to_string(MT_POLICY_MAX_LAYERS));
+  MT_REQUIRE(h, L >= 1 && L <= MT_POLICY_MAX_LAYERS, nm + ".n_layers must be 1.." + std::to_string(MT_POLICY_MAX_LAYERS));
   int widest = 0;
   for (int l = 0; l + 1 < L; ++l) {
     MT_REQUIRE(h, p->width[l] >= 1 && p->width[l] <= MT_POLICY_MAX_WIDTH,
-               "mt_policy.width[" + std::to_string(l) + "] must be 1.." + std::to_string(MT_POLICY_MAX_WIDTH));
+               nm + ".width[" + std::to_string(l) + "] must be 1.." + std::to_string(MT_POLICY_MAX_WIDTH));
     widest = std::max(widest, (int)p->width[l]);
   }
-  MT_REQUIRE(h, L == 1 || p->hidden_act == MT_ACT_TANH || p->hidden_act == MT_ACT_RELU, "mt_policy.hidden_act must be MT_ACT_TANH or MT_ACT_RELU");
-  MT_REQUIRE(h, p->out_act == MT_ACT_TANH || p->out_act == MT_ACT_IDENTITY, "mt_policy.out_act must be MT_ACT_TANH or MT_ACT_IDENTITY");
+  MT_REQUIRE(h, L == 1 || p->hidden_act == MT_ACT_TANH || p->hidden_act == MT_ACT_RELU, nm + ".hidden_act must be MT_ACT_TANH or MT_ACT_RELU");
+  MT_REQUIRE(h, p->out_act == MT_ACT_TANH || p->out_act == MT_ACT_IDENTITY, nm + ".out_act must be MT_ACT_TANH or MT_ACT_IDENTITY");
   // (bit patterns: the build is -ffinite-math-only)
   MT_REQUIRE(h, first_unusable(&p->lo, 1, kMaxAngleBits) < 0 && first_unusable(&p->hi, 1, kMaxAngleBits) < 0,
-             "mt_policy.lo / hi must be finite and within +-32768 degrees");
-  MT_REQUIRE(h, p->lo <= p->hi, "mt_policy.lo must be <= hi");
-  MT_REQUIRE(h, first_unusable(&p->out_scale, 1, kMaxFiniteBits) < 0, "mt_policy.out_scale must be finite");
+             nm + ".lo / hi must be finite and within +-32768 degrees");
+  MT_REQUIRE(h, p->lo <= p->hi, nm + ".lo must be <= hi");
+  MT_REQUIRE(h, first_unusable(&p->out_scale, 1, kMaxFiniteBits) < 0, nm + ".out_scale must be finite");
   bool noisy = false;
   for (int j = 0; j < MT_MAX_DOF; ++j) {
     MT_REQUIRE(h, first_unusable(&p->sigma[j], 1, kMaxFiniteBits) < 0 && p->sigma[j] >= 0.f,
-               "mt_policy.sigma[" + std::to_string(j) + "] must be finite and >= 0");
+               nm + ".sigma[" + std::to_string(j) + "] must be finite and >= 0");
     noisy |= j < h->D && p->sigma[j] > 0.f;
   }
-  if (!fusable(h)) return fail_unfusable(h, "mt_rollout_policy");
-  if (!h->is_reset) return fail(h, MT_ERR_STATE, "mt_rollout_policy before mt_reset / mt_reset_random");
+  if (!fusable(h)) return fail_unfusable(h, who);
+  if (!h->is_reset) return fail(h, MT_ERR_STATE, std::string(who) + " before mt_reset / mt_reset_random");
   if (p->n_steps == 0) return MT_OK;
   for (int l = 0; l < L; ++l)
-    MT_REQUIRE(h, p->weight[l] != nullptr && p->bias[l] != nullptr, "mt_policy.weight / bias [" + std::to_string(l) + "] is NULL");
-  MT_REQUIRE(h, !p->action_log || p->act_ld >= h->n, "mt_policy.act_ld is smaller than n_envs");
-  MT_REQUIRE(h, !p->obs_log || p->obs_ld >= h->n, "mt_policy.obs_ld is smaller than n_envs");
-  MT_REQUIRE(h, !(p->reward_log || p->done_log) || p->log_ld >= h->n, "mt_policy.log_ld is smaller than n_envs");
-  MT_ENTER(h);
+    MT_REQUIRE(h, p->weight[l] != nullptr && p->bias[l] != nullptr, nm + ".weight / bias [" + std::to_string(l) + "] is NULL");
+  MT_REQUIRE(h, !p->action_log || p->act_ld >= h->n, nm + ".act_ld is smaller than n_envs");
+  MT_REQUIRE(h, !p->obs_log || p->obs_ld >= h->n, nm + ".obs_ld is smaller than n_envs");
+  MT_REQUIRE(h, !(p->reward_log || p->done_log) || p->log_ld >= h->n, nm + ".log_ld is smaller than n_envs");
+  out->widest = widest;
+  out->noisy = noisy;
+  return MT_OK;
+}
+// ... the launch (the caller has entered the handle: MT_ENTER): block b reads the weights of member b / blocks_per_member,
+// member_pitch floats behind member 0's
+static int rollout_policy_run(mt_handle h, const struct mt_policy* p, const PolicyScreen& sc, uint32_t blocks_per_member, int64_t member_pitch) {
+  const bool auto_reset = (p->flags & MT_POLICY_AUTO_RESET) != 0, dry = (p->flags & MT_POLICY_DRY_RUN) != 0;
+  const int L = p->n_layers, widest = sc.widest;
+  const bool noisy = sc.noisy;
   PolicyArgs r{};
   const bool see_pose = (p->flags & MT_POLICY_SEE_POSE) != 0;
   int n_in = 3 * h->K + (see_pose ? h->D : 0);
@@ -2296,6 +2308,8 @@ int mt_rollout_policy(mt_handle h, const struct mt_policy* p) {
   r.seed_lo = (uint32_t)p->seed;
   r.seed_hi = (uint32_t)(p->seed >> 32);
   r.radius = h->cfg.radius;
+  r.blocks_per_member = blocks_per_member;
+  r.member_pitch = member_pitch;
   if (auto_reset) {  // what commit_tape does ahead of a re-arming launch
     h->args.seed_lo = (uint32_t)p->seed;
     h->args.seed_hi = (uint32_t)(p->seed >> 32);
@@ -2308,6 +2322,207 @@ int mt_rollout_policy(mt_handle h, const struct mt_policy* p) {
     h->codes_valid = false;             // the kernel writes targets as floats only
   }
   return check_launch(h, "rollout_policy_kernel");
+}
+
+int mt_rollout_policy(mt_handle h, const struct mt_policy* p) {
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  MT_REQUIRE(h, p != nullptr, "policy is NULL");
+  MT_REQUIRE(h, p->struct_size == (int32_t)sizeof(struct mt_policy), "mt_policy.struct_size does not match this library");
+  MT_REQUIRE(h, p->reserved == 0, "mt_policy.reserved must be 0");
+  PolicyScreen sc;
+  int rc = rollout_policy_screen(h, p, "mt_policy", "mt_rollout_policy", &sc);
+  if (rc || p->n_steps == 0) return rc;
+  MT_ENTER(h);
+  return rollout_policy_run(h, p, sc, 1u, 0);
+}
+
+// ---- mt_es_sample, mt_rollout_population, mt_es ------------------------------------------------------------------------
+// The population's shape against the handle's: M even, G = n / M a multiple of the rollout block.
+static int population_shape(mt_handle h, int32_t M, const std::string& nm, int64_t* G) {
+  MT_REQUIRE(h, M >= 2 && M <= MT_ES_MAX_MEMBERS && M % 2 == 0,
+             nm + ".n_members must be even (antithetic pairs), 2.." + std::to_string(MT_ES_MAX_MEMBERS));
+  MT_REQUIRE(h, h->n % M == 0, nm + ".n_members must divide n_envs: member m owns the G = n_envs / n_members envs [mG, (m+1)G)");
+  *G = h->n / M;
+  MT_REQUIRE(h, *G % kBlock == 0, nm + ": G = n_envs / n_members must be a multiple of " + std::to_string(kBlock) +
+                                      ", the rollout block: a block reads one member's weights");
+  return MT_OK;
+}
+// struct mt_population as the struct mt_policy of its member 0 (`q`), with the shape rules and P, the length of theta
+static int population_policy(mt_handle h, const struct mt_population* p, const std::string& nm, struct mt_policy* q, int64_t* P, int64_t* G) {
+  int rc = population_shape(h, p->n_members, nm, G);
+  if (rc) return rc;
+  const int L = p->n_layers;
+  MT_REQUIRE(h, L >= 1 && L <= MT_POLICY_MAX_LAYERS, nm + ".n_layers must be 1.." + std::to_string(MT_POLICY_MAX_LAYERS));
+  for (int l = 0; l + 1 < L; ++l)
+    MT_REQUIRE(h, p->width[l] >= 1 && p->width[l] <= MT_POLICY_MAX_WIDTH,
+               nm + ".width[" + std::to_string(l) + "] must be 1.." + std::to_string(MT_POLICY_MAX_WIDTH));
+  MT_REQUIRE(h, (p->flags & ~(MT_POLICY_AUTO_RESET | MT_POLICY_DRY_RUN | MT_POLICY_SEE_POSE)) == 0, nm + ".flags: unknown MT_POLICY_* flag");
+  *q = mt_policy{};
+  int64_t off = 0;
+  int n_in = 3 * h->K + ((p->flags & MT_POLICY_SEE_POSE) ? h->D : 0);
+  for (int l = 0; l < L; ++l) {  // W_l (out, in) | b_l (out,)
+    const int n_out = (l + 1 < L) ? p->width[l] : h->D;
+    q->weight[l] = p->pop ? p->pop + off : nullptr;
+    off += (int64_t)n_out * n_in;
+    q->bias[l] = p->pop ? p->pop + off : nullptr;
+    off += n_out;
+    n_in = n_out;
+  }
+  *P = off;
+  MT_REQUIRE(h, p->pitch >= off, nm + ".pitch is smaller than P = " + std::to_string(off) + ", the policy's parameter count");
+  MT_REQUIRE(h, !p->fitness_out || p->return_out, nm + ".fitness_out needs return_out");
+  q->struct_size = (int32_t)sizeof(struct mt_policy);
+  q->n_steps = p->n_steps;
+  q->n_layers = L;
+  q->width[0] = p->width[0];
+  q->width[1] = p->width[1];
+  q->hidden_act = p->hidden_act;
+  q->out_act = p->out_act;
+  q->out_scale = p->out_scale;
+  q->lo = p->lo;
+  q->hi = p->hi;
+  q->flags = p->flags;
+  q->action_log = p->action_log;
+  q->act_ld = p->act_ld;
+  q->obs_log = p->obs_log;
+  q->obs_ld = p->obs_ld;
+  q->reward_log = p->reward_log;
+  q->done_log = p->done_log;
+  q->log_ld = p->log_ld;
+  q->return_out = p->return_out;
+  q->seed = p->seed;
+  return MT_OK;
+}
+static float inv_members_envs(int64_t G) { return (float)(1.0 / (double)G); }  // the fp32 nearest to 1 / G
+static bool floats_overlap(const float* p, int64_t np, const float* q, int64_t nq) {
+  const uintptr_t a0 = (uintptr_t)p, a1 = a0 + (uintptr_t)np * 4, b0 = (uintptr_t)q, b1 = b0 + (uintptr_t)nq * 4;
+  return p && q && a0 < b1 && b0 < a1;
+}
+static void launch_es_sums(mt_handle h, const EsArgs& e) {  // a block per member
+  hipLaunchKernelGGL(es_sums_kernel, dim3((unsigned)e.M), dim3(kBlock), 0, h->stream, e);
+}
+static_assert(MT_ES_MAX_MEMBERS == kEsMaxMembers, "the header's member limit is what es_update_kernel's LDS holds");
+
+int mt_es_sample(mt_handle h, const struct mt_es_sample* s) {
+  MT_REQUIRE(h, s != nullptr, "es_sample is NULL");  // (the struct first: its size is checked with or without a handle)
+  MT_REQUIRE(h, s->struct_size == (int32_t)sizeof(struct mt_es_sample), "mt_es_sample.struct_size does not match this library");
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  MT_REQUIRE(h, s->reserved == 0, "mt_es_sample.reserved must be 0");
+  const int M = s->n_members;
+  MT_REQUIRE(h, M >= 2 && M <= MT_ES_MAX_MEMBERS && M % 2 == 0,
+             "mt_es_sample.n_members must be even (antithetic pairs), 2.." + std::to_string(MT_ES_MAX_MEMBERS));
+  MT_REQUIRE(h, s->n_params >= 1 && s->n_params <= ((int64_t)1 << 31), "mt_es_sample.n_params must be 1..2^31");
+  MT_REQUIRE(h, s->pitch >= s->n_params, "mt_es_sample.pitch is smaller than n_params");
+  // (bit patterns: the build is -ffinite-math-only)
+  MT_REQUIRE(h, first_unusable(&s->sigma, 1, kMaxFiniteBits) < 0 && s->sigma > 0.f, "mt_es_sample.sigma must be finite and > 0");
+  MT_REQUIRE(h, s->theta != nullptr && s->pop != nullptr, "mt_es_sample.theta / pop is NULL");
+  MT_REQUIRE(h, !floats_overlap(s->theta, s->n_params, s->pop, (int64_t)(M - 1) * s->pitch + s->n_params), "mt_es_sample.pop overlaps theta");
+  MT_ENTER(h);
+  EsArgs e{};
+  e.theta = const_cast<float*>(s->theta);  // (read only by this kernel)
+  e.pop = s->pop;
+  e.P = s->n_params;
+  e.pitch = s->pitch;
+  e.M = M;
+  e.sigma = s->sigma;
+  e.draw = s->draw;
+  e.seed_lo = (uint32_t)s->seed;
+  e.seed_hi = (uint32_t)(s->seed >> 32);
+  hipLaunchKernelGGL(es_sample_kernel, dim3(grid_for(e.P).x, (unsigned)(M / 2)), dim3(kBlock), 0, h->stream, e);
+  return check_launch(h, "es_sample_kernel");
+}
+
+int mt_rollout_population(mt_handle h, const struct mt_population* p) {
+  MT_REQUIRE(h, p != nullptr, "population is NULL");  // (the struct first: its size is checked with or without a handle)
+  MT_REQUIRE(h, p->struct_size == (int32_t)sizeof(struct mt_population), "mt_population.struct_size does not match this library");
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  MT_REQUIRE(h, p->reserved == 0, "mt_population.reserved must be 0");
+  struct mt_policy q;
+  int64_t P = 0, G = 0;
+  int rc = population_policy(h, p, "mt_population", &q, &P, &G);
+  if (rc) return rc;
+  PolicyScreen sc;
+  rc = rollout_policy_screen(h, &q, "mt_population", "mt_rollout_population", &sc);
+  if (rc || p->n_steps == 0) return rc;
+  MT_ENTER(h);
+  rc = rollout_policy_run(h, &q, sc, (uint32_t)(G / kBlock), p->pitch);
+  if (rc || !p->fitness_out) return rc;
+  EsArgs e{};
+  e.M = p->n_members;
+  e.returns = p->return_out;
+  e.G = G;
+  e.inv_g = inv_members_envs(G);
+  e.fitness = p->fitness_out;
+  launch_es_sums(h, e);
+  return check_launch(h, "es_sums_kernel");
+}
+
+int mt_es(mt_handle h, const struct mt_es* s) {
+  MT_REQUIRE(h, s != nullptr, "es is NULL");  // (the struct first: its size is checked with or without a handle)
+  MT_REQUIRE(h, s->struct_size == (int32_t)sizeof(struct mt_es), "mt_es.struct_size does not match this library");
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  MT_REQUIRE(h, s->reserved == 0, "mt_es.reserved must be 0");
+  MT_REQUIRE(h, s->pop.struct_size == (int32_t)sizeof(struct mt_population), "mt_es.pop.struct_size does not match this library");
+  MT_REQUIRE(h, s->pop.reserved == 0, "mt_es.pop.reserved must be 0");
+  MT_REQUIRE(h, (s->flags & ~(MT_ES_INPLACE | MT_ES_UPDATE_ONLY)) == 0, "mt_es.flags: unknown MT_ES_* flag");
+  MT_REQUIRE(h, s->shaping == MT_ES_SHAPE_RANK || s->shaping == MT_ES_SHAPE_RAW, "mt_es.shaping must be MT_ES_SHAPE_RANK or MT_ES_SHAPE_RAW");
+  const bool inplace = (s->flags & MT_ES_INPLACE) != 0, update_only = (s->flags & MT_ES_UPDATE_ONLY) != 0;
+  const bool raw = s->shaping == MT_ES_SHAPE_RAW;
+  MT_REQUIRE(h, first_unusable(&s->sigma, 1, kMaxFiniteBits) < 0 && s->sigma > 0.f, "mt_es.sigma must be finite and > 0");
+  MT_REQUIRE(h, !inplace || first_unusable(&s->lr, 1, kMaxFiniteBits) < 0, "mt_es.lr must be finite");
+  struct mt_policy q;
+  int64_t P = 0, G = 0;
+  int rc = population_policy(h, &s->pop, "mt_es.pop", &q, &P, &G);
+  if (rc) return rc;
+  PolicyScreen sc;
+  rc = rollout_policy_screen(h, &q, "mt_es.pop", "mt_es", &sc);
+  if (rc || s->pop.n_steps == 0) return rc;
+  const int M = s->pop.n_members, T = s->pop.n_steps;
+  MT_REQUIRE(h, s->theta != nullptr && s->grad_out != nullptr && s->coeff_out != nullptr, "mt_es.theta / grad_out / coeff_out is NULL");
+  MT_REQUIRE(h, s->pop.return_out != nullptr, "mt_es.pop.return_out is NULL: the update reads the return row");
+  const int64_t pop_floats = (int64_t)(M - 1) * s->pop.pitch + P;
+  MT_REQUIRE(h, !floats_overlap(s->theta, P, s->grad_out, P), "mt_es.grad_out overlaps theta");
+  MT_REQUIRE(h, !floats_overlap(s->theta, P, s->pop.pop, pop_floats) && !floats_overlap(s->grad_out, P, s->pop.pop, pop_floats),
+             "mt_es.pop.pop overlaps theta / grad_out");
+  // |coeff| <= 2 c_max, |bytesum - 510| <= 510, M / 2 pairs: A_i stays within int64
+  const double c_max = raw ? (double)G * 127.0 * (double)T : 2.0 * (double)(M - 1);
+  MT_REQUIRE(h, (double)M * c_max * 510.0 < 4.0e18, "mt_es: n_members * G * n_steps is too large for the update's int64 sums");
+  MT_ENTER(h);
+  EsArgs e{};
+  e.theta = s->theta;
+  e.pop = const_cast<float*>(s->pop.pop);
+  e.P = P;
+  e.pitch = s->pop.pitch;
+  e.M = M;
+  e.sigma = s->sigma;
+  e.draw = s->draw;
+  e.seed_lo = (uint32_t)s->pop.seed;
+  e.seed_hi = (uint32_t)(s->pop.seed >> 32);
+  e.returns = s->pop.return_out;
+  e.G = G;
+  e.inv_g = inv_members_envs(G);
+  // the fp32 nearest to KZ / (M sigma 2 (M - 1)) or KZ / (M sigma G), in double from the fp32 KZ and the fp32 sigma
+  e.scale = (float)((double)kPlanNoiseScale / ((double)M * (double)s->sigma * (raw ? (double)G : 2.0 * (double)(M - 1))));
+  e.lr = s->lr;
+  e.raw = raw ? 1u : 0u;
+  e.inplace = inplace ? 1u : 0u;
+  e.coeff = reinterpret_cast<long long*>(s->coeff_out);
+  e.sums = e.coeff + M / 2;
+  e.fitness = s->pop.fitness_out;
+  e.best = s->best_out;
+  e.grad = s->grad_out;
+  if (!update_only) {
+    hipLaunchKernelGGL(es_sample_kernel, dim3(grid_for(P).x, (unsigned)(M / 2)), dim3(kBlock), 0, h->stream, e);
+    rc = check_launch(h, "es_sample_kernel");
+    if (rc) return rc;
+    rc = rollout_policy_run(h, &q, sc, (uint32_t)(G / kBlock), s->pop.pitch);
+    if (rc) return rc;
+  }
+  launch_es_sums(h, e);
+  rc = check_launch(h, "es_sums_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(es_update_kernel, grid_for(P), dim3(kBlock), (size_t)(M + M / 2) * sizeof(long long), h->stream, e);
+  return check_launch(h, "es_update_kernel");
 }
 
 int mt_shoot(mt_handle h, const struct mt_shoot* s) {

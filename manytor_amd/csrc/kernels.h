@@ -2539,6 +2539,10 @@ struct PolicyArgs {
   uint32_t auto_reset, dry_run;
   uint32_t seed_lo, seed_hi;  // keys the noise stream and the targets of re-armed envs
   float radius;
+  // mt_rollout_population: block b reads member b / blocks_per_member's weights, member_pitch floats behind the previous
+  // member's in every w[l] and b[l] (a scalar computation: a block never straddles two members).  mt_rollout_policy: 1 and 0.
+  uint32_t blocks_per_member;
+  int64_t member_pitch;
 };
 
 using weight_ptr = __attribute__((address_space(4))) const float*;  // constant address space: uniform reads are scalar loads
@@ -2655,8 +2659,9 @@ __global__ __launch_bounds__(kBlock) void rollout_policy_kernel(const StepArgs a
   const TargetColumn<kBlock> tc{tile + threadIdx.x};
   const bool commit = r.dry_run == 0;  // (wave-uniform: a launch argument)
   const int L = r.L, IN = r.n_in[0];
-  const weight_ptr w0 = as_weights(r.w[0]), b0 = as_weights(r.b[0]);
-  const weight_ptr wl = as_weights(r.w[L - 1]), bl = as_weights(r.b[L - 1]);  // the output layer (the first one when L == 1)
+  const int64_t member = (int64_t)(blockIdx.x / r.blocks_per_member) * r.member_pitch;  // (block-uniform; 0 for one policy)
+  const weight_ptr w0 = as_weights(r.w[0]) + member, b0 = as_weights(r.b[0]) + member;
+  const weight_ptr wl = as_weights(r.w[L - 1]) + member, bl = as_weights(r.b[L - 1]) + member;  // the output layer (the first one when L == 1)
 
   const uint32_t all_alive = all_alive_mask(a.K);
   float g[D];
@@ -2721,7 +2726,7 @@ __global__ __launch_bounds__(kBlock) void rollout_policy_kernel(const StepArgs a
           float h1[W];
 #pragma unroll
           for (int o = 0; o < W; ++o) h1[o] = 0.f;
-          policy_hidden<W>(as_weights(r.w[1]), as_weights(r.b[1]), r.n_in[1], r.n_out[1], r.hidden_act, h0, h1);
+          policy_hidden<W>(as_weights(r.w[1]) + member, as_weights(r.b[1]) + member, r.n_in[1], r.n_out[1], r.hidden_act, h0, h1);
 #pragma unroll
           for (int j = 0; j < D; ++j) y[j] = policy_dot<W>(wl + (int64_t)j * r.n_in[2], bl[j], r.n_in[2], h1);
         }
@@ -2826,6 +2831,128 @@ __global__ __launch_bounds__(kBlock) void rollout_policy_kernel(const StepArgs a
   if (ended) str(a.episodes, o4, episode);
   if (dirty)
     for (int k = 0; k < 3 * a.K; ++k) str(a.points + (int64_t)k * ld, o4, tc.row(k));
+}
+
+// ---------------------------------------------------------------------------
+// An evolution-strategies generation (mt_es_sample, mt_es): the planners' three levels in parameter space.  The scoring is
+// rollout_policy_kernel with a member's row as the weights (PolicyArgs::member_pitch); the kernels here are what surrounds
+// it, and none of them touches a handle's state.
+//   es_sample_kernel  a thread per (parameter i, pair p): eps from word i & 3 of the pair's Philox block i >> 2, rows 2p and
+//                     2p + 1 written as theta + sigma * eps and theta - sigma * eps (a multiply, then an add or a subtract)
+//   es_sums_kernel    a block per member: the member's G returns summed in int64 (integer-valued floats: the order is
+//                     free) -> sums[m], fitness[m]
+//   es_update_kernel  every block first ranks for itself: the M sums into LDS, the centred mid-ranks (an O(M^2) count over
+//                     LDS broadcast reads) or the raw sums as the pair differences c_2p - c_2p+1, kept in LDS (block 0 also
+//                     writes them out, and best); then a thread per parameter: A_i = sum_p coeff[p] * (bytesum(p, i) - 510)
+//                     in int64, the noise regenerated; grad_i = (float)A_i * scale; theta_i += lr * grad_i.  Ranking once per
+//                     block costs M^2 / 512 compare pairs per thread and saves a launch and a serial block.
+// ---------------------------------------------------------------------------
+constexpr int kEsMaxMembers = 4096;  // es_update_kernel keeps M sums and M / 2 coefficients in LDS: 48 KB
+struct EsArgs {
+  float* theta;  // [P]: read by the sample, updated in place by the update when `inplace`
+  float* pop;    // [M][pitch]
+  int64_t P, pitch;
+  int32_t M;
+  float sigma;
+  uint32_t draw, seed_lo, seed_hi;
+  const float* returns;  // [M * G]
+  int64_t G;
+  float inv_g, scale, lr;
+  uint32_t raw, inplace;
+  long long* coeff;  // [M / 2]: c_2p - c_2p+1
+  long long* sums;   // [M]: S_m (NULL: fitness only)
+  float* fitness;    // [M]
+  int32_t* best;     // [1]
+  float* grad;       // [P]
+};
+
+// word i & 3 of pair p's block i >> 2 of the ES stream
+__device__ __forceinline__ uint32_t es_word(uint64_t seed, uint32_t p, uint32_t draw, int64_t i) {
+  const u32x4 b = stream_block(seed, (uint64_t)p, kTagES, draw, (uint32_t)(i >> 2));
+  const uint32_t q = (uint32_t)i & 3u;
+  return q == 0u ? b.x : q == 1u ? b.y : q == 2u ? b.z : b.w;
+}
+
+__global__ __launch_bounds__(kBlock) void es_sample_kernel(const EsArgs r) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= r.P) return;
+  const uint32_t p = blockIdx.y;
+  const uint64_t seed = ((uint64_t)r.seed_hi << 32) | r.seed_lo;
+  const float th = r.theta[i];
+  const float se = r.sigma * plan_noise(es_word(seed, p, r.draw, i));
+  float* row = r.pop + (int64_t)(2u * p) * r.pitch + i;
+  row[0] = th + se;
+  row[r.pitch] = th - se;
+}
+
+__global__ __launch_bounds__(kBlock) void es_sums_kernel(const EsArgs r) {
+  __shared__ long long part[kBlock / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int m = blockIdx.x;  // (the grid is M blocks)
+  const float* row = r.returns + (int64_t)m * r.G;
+  long long acc = 0;
+  for (int64_t k = threadIdx.x; k < r.G; k += kBlock) acc += (long long)(int32_t)row[k];
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off);
+  if (lane == 0) part[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    long long s = 0;
+#pragma unroll
+    for (int w = 0; w < kBlock / 64; ++w) s += part[w];
+    if (r.sums) r.sums[m] = s;
+    if (r.fitness) r.fitness[m] = (float)s * r.inv_g;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void es_update_kernel(const EsArgs r) {
+  extern __shared__ __attribute__((aligned(16))) long long es_lds[];  // [M] sums, [M / 2] coefficients
+  const int M = r.M;
+  long long* es_sum = es_lds;
+  long long* coeff = es_lds + M;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int m = threadIdx.x; m < M; m += kBlock) es_sum[m] = r.sums[m];
+  __syncthreads();
+  for (int p = threadIdx.x; p < M / 2; p += kBlock) {
+    const long long s0 = es_sum[2 * p], s1 = es_sum[2 * p + 1];
+    long long c0 = s0, c1 = s1;
+    if (!r.raw) {  // centred mid-ranks: 2 #{S_j < S_m} + #{j != m : S_j == S_m}
+      c0 = c1 = -1;  // (j == m counts itself once below)
+      for (int j = 0; j < M; ++j) {
+        const long long s = es_sum[j];
+        c0 += s < s0 ? 2 : (s == s0 ? 1 : 0);
+        c1 += s < s1 ? 2 : (s == s1 ? 1 : 0);
+      }
+    }
+    coeff[p] = c0 - c1;
+    if (blockIdx.x == 0) r.coeff[p] = c0 - c1;
+  }
+  if (blockIdx.x == 0 && r.best && wave == 0) {  // the lowest m with the largest sum
+    long long bs = es_sum[lane < M ? lane : 0];
+    int bm = lane < M ? lane : 0;
+    for (int m = lane + 64; m < M; m += 64)
+      if (es_sum[m] > bs) bs = es_sum[m], bm = m;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const long long os = __shfl_down(bs, off);
+      const int om = __shfl_down(bm, off);
+      if (os > bs || (os == bs && om < bm)) bs = os, bm = om;
+    }
+    if (lane == 0) r.best[0] = bm;
+  }
+  __syncthreads();  // (the last barrier: tail lanes leave behind it)
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= r.P) return;
+  const uint64_t seed = ((uint64_t)r.seed_hi << 32) | r.seed_lo;
+  long long acc = 0;
+  for (int p = 0; p < M / 2; ++p)
+    acc += coeff[p] * (long long)noise_byte_sum(es_word(seed, (uint32_t)p, r.draw, i));
+  const float g = (float)acc * r.scale;
+  r.grad[i] = g;
+  if (r.inplace) {
+    const float d = r.lr * g;
+    r.theta[i] = r.theta[i] + d;
+  }
 }
 
 // ---------------------------------------------------------------------------

@@ -17,6 +17,7 @@ constexpr uint32_t kTagAction = 1u;
 constexpr uint32_t kTagTarget = 2u;
 constexpr uint32_t kTagPlan = 3u;  // mt_cem / mt_sample_plans: the noise of candidate plans
 constexpr uint32_t kTagPolicy = 4u;  // mt_rollout_policy: the exploration noise of a policy's actions
+constexpr uint32_t kTagES = 5u;  // mt_es_sample / mt_es: parameter noise, keyed by the antithetic pair in the env's place
 
 struct u32x4 {
   uint32_t x, y, z, w;
@@ -90,6 +91,15 @@ __host__ __device__ __forceinline__ float plan_noise(uint32_t w) {
   const uint32_t s = (w & 0xFFu) + ((w >> 8) & 0xFFu) + ((w >> 16) & 0xFFu) + (w >> 24);
 #endif
   return (float)((int32_t)s - 510) * kPlanNoiseScale;
+}
+// The same variate before its scale, as the integer it is: mt_es sums these exactly (plan_noise(w) = noise_byte_sum(w) * KZ).
+__host__ __device__ __forceinline__ int32_t noise_byte_sum(uint32_t w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t s = __builtin_amdgcn_sad_u8(w, 0u, 0u);
+#else
+  const uint32_t s = (w & 0xFFu) + ((w >> 8) & 0xFFu) + ((w >> 16) & 0xFFu) + (w >> 24);
+#endif
+  return (int32_t)s - 510;
 }
 
 }  // namespace mt

@@ -618,6 +618,216 @@ class StepEngine:
         del keep
         return res or None
 
+    # ---- evolution strategies: a population of policies, one row of flat parameters per member ----------------------------
+    def _policy_shapes(self, widths, see_pose=False):
+        """[(out, in), ...] of the linear layers of a policy with hidden `widths` on this engine."""
+        widths = tuple(int(w) for w in widths)
+        if len(widths) > L.POLICY_MAX_LAYERS - 1 or any(not 1 <= w <= L.POLICY_MAX_WIDTH for w in widths):
+            raise ValueError(f"widths must be at most {L.POLICY_MAX_LAYERS - 1} hidden widths of 1..{L.POLICY_MAX_WIDTH}, got {widths}")
+        fan_in, shapes = 3 * self.obj_number + (self.dof if see_pose else 0), []
+        for fan_out in widths + (self.dof,):
+            shapes.append((fan_out, fan_in))
+            fan_in = fan_out
+        return shapes
+
+    def policy_size(self, widths=(), see_pose=False) -> int:
+        """P, the number of floats of a policy with hidden `widths`: sum of out * in + out over its layers."""
+        return sum(o * i + o for o, i in self._policy_shapes(widths, see_pose))
+
+    @staticmethod
+    def flatten_policy(layers):
+        """theta of a policy given as rollout_policy takes it: W0 | b0 | W1 | b1 | ... as one new float32 vector."""
+        import torch
+        if isinstance(layers, torch.nn.Sequential):
+            pairs = [(m.weight, m.bias) for m in layers if isinstance(m, torch.nn.Linear)]
+        else:
+            pairs = [tuple(p) for p in layers]
+        return torch.cat([t.detach().reshape(-1) for pair in pairs for t in pair]).to(torch.float32).contiguous()
+
+    def unflatten_policy(self, theta, widths=(), see_pose=False):
+        """[(weight, bias), ...] VIEWS of `theta` (P floats, a row of a population included): what rollout_policy accepts."""
+        shapes = self._policy_shapes(widths, see_pose)
+        need = sum(o * i + o for o, i in shapes)
+        if theta.dim() != 1 or theta.shape[0] < need or theta.stride(0) != 1:
+            raise ValueError(f"theta must be a dense vector of at least P = {need} floats, got shape {tuple(theta.shape)}")
+        out, off = [], 0
+        for o, i in shapes:
+            out.append((theta[off:off + o * i].view(o, i), theta[off + o * i:off + o * i + o]))
+            off += o * i + o
+        return out
+
+    def _members(self, members):
+        m = int(members)
+        if m < 2 or m % 2 or m > L.ES_MAX_MEMBERS:
+            raise ValueError(f"members must be even (antithetic pairs), 2..{L.ES_MAX_MEMBERS}, got {members}")
+        return m
+
+    def _flat_vector(self, t, name, size=None):
+        import torch
+        dev = torch.device("cuda", self.device)
+        if not _is_torch_tensor(t) or t.dtype != torch.float32 or t.device != dev or t.dim() != 1 or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous 1-d float32 tensor on {dev}")
+        if size is not None and t.shape[0] != size:
+            raise ValueError(f"{name} must have P = {size} elements, got {t.shape[0]}")
+        return t
+
+    def _population_tensor(self, pop, members, size, name="pop"):
+        import torch
+        dev = torch.device("cuda", self.device)
+        if (not _is_torch_tensor(pop) or pop.dtype != torch.float32 or pop.device != dev or pop.dim() != 2
+                or pop.shape[0] != members or (pop.shape[1] > 1 and pop.stride(1) != 1)):
+            raise ValueError(f"{name} must be a float32 ({members}, >= P) tensor on {dev} with dense rows")
+        pitch = int(pop.stride(0))
+        if pop.shape[1] < size or pitch < size:
+            raise ValueError(f"{name}: rows of {pop.shape[1]} floats, pitch {pitch}: smaller than P = {size}")
+        return pitch
+
+    @staticmethod
+    def _positive(sigma, name="sigma"):
+        s = float(np.float32(sigma))
+        if not (np.isfinite(s) and s > 0.0):
+            raise ValueError(f"{name} must be finite and > 0, got {sigma!r}")
+        return s
+
+    def sample_population(self, theta, sigma, *, members, draw=0, seed=0x5EED, out=None):
+        """The (M, P) population es() with the same arguments scores (mt_es_sample): row 2p is theta + sigma * eps_p, row
+        2p + 1 theta - sigma * eps_p, eps the library's counter-based noise keyed by (seed, pair, draw, parameter).  `theta`
+        is a CUDA float32 vector read in place; `out`, if given, is a float32 (M, >= P) tensor with dense rows whose words
+        past P are left alone.  Returns the population.  Stream rules as rollout_actions."""
+        import torch
+        m, s = self._members(members), self._positive(sigma)
+        theta = self._flat_vector(theta, "theta")
+        p = int(theta.shape[0])
+        if p < 1:
+            raise ValueError("theta is empty")
+        if out is None:
+            out = torch.empty((m, p), dtype=torch.float32, device=theta.device)
+        pitch = self._population_tensor(out, m, p, "out")
+        arg = L.MtEsSample()
+        arg.struct_size = C.sizeof(L.MtEsSample)
+        arg.n_members, arg.n_params = m, p
+        arg.theta, arg.pop, arg.pitch = theta.data_ptr(), out.data_ptr(), pitch
+        arg.sigma, arg.draw, arg.seed = s, int(draw) & 0xFFFFFFFF, int(seed)
+        arg.reserved = 0
+        self._torch_call(self._lib.mt_es_sample, C.byref(arg), commits=False)
+        return out
+
+    def _population_arg(self, arg, pop, members, steps, widths, hidden, out, out_scale, see_pose, seed, auto_reset, dry_run, lo, hi,
+                        res, log, actions, observations):
+        """Fills a struct mt_population and allocates the logs asked for into `res`; returns (M, P, T)."""
+        import torch
+        if auto_reset and dry_run:
+            raise ValueError("dry_run and auto_reset exclude each other: the re-arm writes the return ring")
+        for name, v, allowed in (("hidden", hidden, ("tanh", "relu")), ("out", out, ("tanh", "identity"))):
+            if v not in allowed:
+                raise ValueError(f"{name} must be one of {allowed}, got {v!r}")
+        m = self._members(members)
+        n, d, T = self.n_envs, self.dof, int(steps)
+        if not 0 <= T <= 65535:
+            raise ValueError(f"steps must be 0..65535, got {T}")
+        if n % m or (n // m) % 256:
+            raise ValueError(f"n_envs = {n} must be members * G with G a multiple of 256 (the rollout block), got members = {m}")
+        shapes = self._policy_shapes(widths, see_pose)
+        p = sum(o * i + o for o, i in shapes)
+        pitch = self._population_tensor(pop, m, p)
+        dev = pop.device
+        if log:
+            res["reward"] = torch.empty((T, n), dtype=torch.int8, device=dev)
+            res["done"] = torch.empty((T, n), dtype=torch.uint8, device=dev)
+        if actions:
+            res["actions"] = torch.empty((T, d, n), dtype=torch.float32, device=dev)
+        if observations:
+            res["observations"] = torch.empty((T, shapes[0][1], n), dtype=torch.float32, device=dev)
+        arg.struct_size = C.sizeof(L.MtPopulation)
+        arg.n_steps, arg.n_members, arg.n_layers = T, m, len(shapes)
+        for l, (o, _) in enumerate(shapes[:-1]):
+            arg.width[l] = o
+        arg.hidden_act, arg.out_act = self._ACTIVATIONS[hidden], self._ACTIVATIONS[out]
+        arg.pop, arg.pitch = pop.data_ptr(), pitch
+        arg.out_scale, arg.lo, arg.hi = float(out_scale), float(lo), float(hi)
+        arg.flags = ((L.POLICY_AUTO_RESET if auto_reset else 0) | (L.POLICY_DRY_RUN if dry_run else 0)
+                     | (L.POLICY_SEE_POSE if see_pose else 0))
+        arg.action_log = res["actions"].data_ptr() if actions and T else None
+        arg.obs_log = res["observations"].data_ptr() if observations and T else None
+        arg.reward_log = res["reward"].data_ptr() if log and T else None
+        arg.done_log = res["done"].data_ptr() if log and T else None
+        arg.act_ld = arg.obs_ld = arg.log_ld = n
+        arg.seed = int(seed)
+        arg.reserved = 0
+        return m, p, T
+
+    def rollout_population(self, pop, steps, *, widths=(), hidden="tanh", out="tanh", out_scale=180.0, see_pose=False,
+                           seed=0x5EED, auto_reset=False, lo=-180., hi=180., log=False, returns=False, actions=False,
+                           observations=False, dry_run=False):
+        """M policies scored in ONE launch (mt_rollout_population): row m of `pop` -- a CUDA float32 (M, >= P) tensor with
+        dense rows, each row the flat parameters of a policy with hidden `widths` (flatten_policy's layout) -- drives the
+        G = N / M envs [mG, (m+1)G) as rollout_policy would with unflatten_policy(pop[m]) as its layers, bit for bit; there
+        is no action noise.  M is even and G a multiple of 256.  Returns rollout_policy's dict (log / returns / actions /
+        observations) plus `fitness` (M,): each member's mean return over its envs.  The other keywords, the state
+        afterwards and the stream behaviour are rollout_policy's."""
+        import torch
+        res = {}
+        arg = L.MtPopulation()
+        m, _, T = self._population_arg(arg, pop, pop.shape[0] if _is_torch_tensor(pop) and pop.dim() == 2 else 0, steps, widths, hidden,
+                                       out, out_scale, see_pose, seed, auto_reset, dry_run, lo, hi, res, log, actions, observations)
+        ret = torch.zeros(self.n_envs, dtype=torch.float32, device=pop.device)
+        res["fitness"] = torch.zeros(m, dtype=torch.float32, device=pop.device)
+        if returns:
+            res["returns"] = ret
+        arg.return_out, arg.fitness_out = ret.data_ptr(), res["fitness"].data_ptr()
+        self._torch_call(self._lib.mt_rollout_population, C.byref(arg), commits=not dry_run and T > 0)
+        return res
+
+    def es(self, theta, sigma, *, members, steps, widths=(), shaping="rank", lr=None, inplace=False, draw=0, seed=0x5EED,
+           hidden="tanh", out="tanh", out_scale=180.0, see_pose=False, auto_reset=False, dry_run=False, lo=-180., hi=180.,
+           log=False, population=None, returns=None, update_only=False):
+        """One generation of an antithetic evolution strategy in one call (mt_es): `members` perturbed copies of `theta`
+        (sample_population's, with the same sigma / draw / seed) are scored over `steps` steps (rollout_population's, each
+        member on its own N / M envs), and the gradient estimate follows from the members' integer return sums:
+        shaping="rank" weighs a member by its centred mid-rank, "raw" by its return sum.  Four launches, no host wait.
+        Returns a dict of device tensors: `grad` (P,), ascent direction of the mean return; `fitness` (M,); `best` (1,)
+        int32, the lowest member with the largest sum; `returns` (N,); `population` (M, P); `sums` (M,) int64, the members'
+        return sums, and `coeff` (M / 2,) int64, the pair weights they shape into; with log=True `reward` / `done` as rollout_policy.  inplace=True also does theta += lr * grad.
+        `population` / `returns` may be given as workspaces (the population as for sample_population's `out`).
+        update_only=True skips sampling and scoring and updates from `returns` as given (integer-valued floats).  The
+        policy keywords, the state afterwards and the stream behaviour are rollout_population's."""
+        import torch
+        if shaping not in ("rank", "raw"):
+            raise ValueError(f"shaping must be 'rank' or 'raw', got {shaping!r}")
+        if inplace and lr is None:
+            raise ValueError("inplace=True needs lr")
+        if update_only and returns is None:
+            raise ValueError("update_only=True needs returns")
+        m, s = self._members(members), self._positive(sigma)
+        p = self.policy_size(widths, see_pose)
+        theta = self._flat_vector(theta, "theta", p)
+        dev = theta.device
+        if population is None:
+            population = torch.empty((m, p), dtype=torch.float32, device=dev)
+        if returns is None:
+            returns = torch.zeros(self.n_envs, dtype=torch.float32, device=dev)
+        elif tuple(self._flat_vector(returns, "returns").shape) != (self.n_envs,):
+            raise ValueError(f"returns must have n_envs = {self.n_envs} elements")
+        res = {}
+        arg = L.MtEs()
+        _, _, T = self._population_arg(arg.pop, population, m, steps, widths, hidden, out, out_scale, see_pose, seed, auto_reset,
+                                       dry_run, lo, hi, res, log, False, False)
+        res.update(grad=torch.zeros(p, dtype=torch.float32, device=dev), fitness=torch.zeros(m, dtype=torch.float32, device=dev),
+                   best=torch.zeros(1, dtype=torch.int32, device=dev), returns=returns, population=population,
+                   coeff=torch.zeros(m // 2 + m, dtype=torch.int64, device=dev))
+        arg.pop.return_out, arg.pop.fitness_out = returns.data_ptr(), res["fitness"].data_ptr()
+        arg.struct_size = C.sizeof(L.MtEs)
+        arg.shaping = L.ES_SHAPE_RAW if shaping == "raw" else L.ES_SHAPE_RANK
+        arg.sigma, arg.lr = s, float(lr) if lr is not None else 0.0
+        arg.draw = int(draw) & 0xFFFFFFFF
+        arg.flags = (L.ES_INPLACE if inplace else 0) | (L.ES_UPDATE_ONLY if update_only else 0)
+        arg.theta, arg.grad_out = theta.data_ptr(), res["grad"].data_ptr()
+        arg.best_out, arg.coeff_out = res["best"].data_ptr(), res["coeff"].data_ptr()
+        arg.reserved = 0
+        self._torch_call(self._lib.mt_es, C.byref(arg), commits=not dry_run and not update_only and T > 0)
+        res["coeff"], res["sums"] = res["coeff"][:m // 2], res["coeff"][m // 2:]
+        return res
+
     def shoot(self, plans, *, layout="soa", commit=0, auto_reset=False, seed=0x5EED, all_returns=False, log=False,
               returns=False):
         """A sampling planner's round in one call (mt_shoot): `plans` holds C candidate tapes of T steps per env, (C, T, D, N)
