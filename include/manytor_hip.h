@@ -28,6 +28,7 @@
 #ifndef MANYTOR_HIP_H
 #define MANYTOR_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -40,7 +41,7 @@ extern "C" {
 #define MT_API
 #endif
 
-#define MT_VERSION 450         /* major*10000 + minor*100 + patch */
+#define MT_VERSION 460        /* major*10000 + minor*100 + patch */
 #define MT_MAX_DOF 8
 #define MT_MAX_TARGETS 32
 #define MT_MAX_RETURN_RING 64
@@ -568,6 +569,82 @@ struct mt_es {
   uint64_t reserved;       /* must be 0 */
 };
 MT_API int mt_es(mt_handle h, const struct mt_es* s);
+
+/* The weighted log-likelihood gradient of the MLP policy: the gradient-based rung on top of mt_rollout_policy's logs
+ * (REINFORCE with coef = reward-to-go, behaviour cloning of a planner's actions with coef = 1 and sigma = 1).
+ *
+ * Samples.  s = (t, i), t < n_steps, i < n_envs: x = obs[t, :, i] (IN floats, obs_log's layout), a = action[t, :, i]
+ * (D floats, action_log's / mt_tape's layout), c = coef[t, i].
+ * mu(x) is mt_rollout_policy's action before noise and clamp, out_scale * out_act(y_L): the same layers, activations and
+ * tanh, evaluated with the same fmaf chains, so mu is bit for bit what mt_rollout_policy computes for that x.
+ *   logp_s = -1/2 sum_j ((a_j - mu_j) / sigma_j)^2                 (constants dropped)
+ *   grad   = scale * sum_s c_s d logp_s / d theta                   (P floats, mt_es's flat layout W0|b0|W1|b1|W2|b2)
+ *   loss   = scale * sum_s c_s logp_s
+ * with tanh' = 1 - h^2 taken from the forward value and relu' = 1 where the forward output is > 0, else 0.  action_log holds
+ * CLAMPED actions; the likelihood ignores the clamp (a clamped a is scored as if the Gaussian had produced it).
+ * Every sigma_j, j < D, must be finite and > 0 (MT_ERR_INVALID_ARG otherwise); behaviour cloning passes sigma = 1.
+ * Skipped samples.  A sample contributes exactly nothing when c == 0 or when any a_j is unusable by the rule of every
+ * tape (NaN, +-inf, beyond +-32768 degrees: the env held its pose): its x and a are then never read into the arithmetic,
+ * NaN among them included.  This is how a caller masks the steps behind `done` (mt_reward_to_go's
+ * MT_RTG_MASK_AFTER_DONE writes such zeros).
+ * Contract.  Two launches on the handle's stream (one when n_steps == 0, which writes zeros), no allocation, no host
+ * wait: legal under stream capture.  Nothing resident is read or written but the handle's shape (n_envs, K, D).
+ * Everything the host can see is screened; grad_out, loss_out and the workspace must not overlap the weights, obs, action
+ * or coef, nor each other.  The workspace holds per-block partial sums, mt_policy_grad_workspace() bytes (a function of
+ * the handle's n_envs and device, the policy's shape and n_steps); a second pass adds them in ascending block order and
+ * applies scale once.  No floating-point atomics: two calls with the same arguments on the same handle give the same
+ * bits.  The bits may depend on n_steps, n_envs and the launch shape (the device's CU count); they do not depend on the
+ * ld's, and a sample's contribution does not depend on the values of other samples.
+ * No word outside the (out, in) matrices, the (out,) vectors and the first n_envs columns of each row of obs, action and
+ * coef is read, whatever the widths (down to 1) and the ld's (>= n_envs). */
+struct mt_policy_grad {    /* as with mt_cem, the type is always written `struct mt_policy_grad` */
+  int32_t struct_size;     /* = sizeof(struct mt_policy_grad), checked */
+  int32_t n_steps;         /* T, 0..65535 */
+  int32_t n_layers;        /* L, as mt_policy */
+  int32_t width[2];
+  int32_t hidden_act;
+  int32_t out_act;
+  const float* weight[3];  /* DEVICE f32, as mt_policy */
+  const float* bias[3];
+  float out_scale;         /* finite */
+  float sigma[MT_MAX_DOF]; /* per joint, degrees: finite, > 0 for j < D (entries behind D: finite, >= 0, not read) */
+  uint32_t flags;          /* MT_POLICY_SEE_POSE only: it fixes IN */
+  const float* obs;    int64_t obs_ld;    /* DEVICE (T, IN, obs_ld) */
+  const float* action; int64_t act_ld;    /* DEVICE (T, D, act_ld) */
+  const float* coef;   int64_t coef_ld;   /* DEVICE (T, coef_ld) f32: the weight c of sample (t, i) */
+  float scale;             /* finite; applied once, at the final conversion */
+  float* grad_out;         /* DEVICE f32 (P,): always written */
+  float* loss_out;         /* DEVICE f32 (1,) or NULL */
+  void* workspace;         /* DEVICE, 4-byte aligned; may be NULL when mt_policy_grad_workspace() is 0 */
+  size_t workspace_bytes;  /* >= mt_policy_grad_workspace() */
+  uint64_t reserved;       /* must be 0 */
+};
+MT_API int mt_policy_grad(mt_handle h, const struct mt_policy_grad* p);
+/* Bytes of workspace mt_policy_grad needs on this handle for a policy of that shape and n_steps (0 for n_steps == 0, and
+ * for arguments mt_policy_grad would refuse). */
+MT_API size_t mt_policy_grad_workspace(mt_handle h, int n_layers, const int32_t width[2], uint32_t flags, int n_steps);
+
+/* The usual sample weights of mt_policy_grad from mt_rollout_policy's logs: the discounted reward-to-go.  One lane per env
+ * runs backwards over t:  R_t = fmaf(gamma, done_t ? 0 : R_t+1, (float)r_t),  R_T = 0;  out[t, i] = R_t - baseline (one
+ * fp32 subtraction).  gamma is an fp32 in [0, 1]; with gamma = 1 every R_t is an integer.  A done flag cuts the sum: with
+ * MT_POLICY_AUTO_RESET the step behind it belongs to the next episode.  MT_RTG_MASK_AFTER_DONE, for logs without
+ * auto-reset (the env steps on after its episode ended): every step behind the env's FIRST done gets exactly 0, which
+ * mt_policy_grad skips.  One launch on the handle's stream, capturable; reads the first n_envs columns of the T rows. */
+#define MT_RTG_MASK_AFTER_DONE 0x1u
+struct mt_reward_to_go {   /* as with mt_cem, the type is always written `struct mt_reward_to_go` */
+  int32_t struct_size;     /* = sizeof(struct mt_reward_to_go), checked */
+  int32_t n_steps;         /* T, 0..65535; 0 is a no-op */
+  const int8_t* reward_log;   /* DEVICE (T, log_ld) */
+  const uint8_t* done_log;    /* DEVICE (T, log_ld) */
+  int64_t log_ld;          /* >= n_envs */
+  float gamma;             /* 0 <= gamma <= 1 */
+  float baseline;          /* finite */
+  float* out;              /* DEVICE f32 (T, out_ld) */
+  int64_t out_ld;          /* >= n_envs */
+  uint32_t flags;          /* MT_RTG_* */
+  uint32_t reserved;       /* must be 0 */
+};
+MT_API int mt_reward_to_go(mt_handle h, const struct mt_reward_to_go* s);
 
 /* Environment.get_observations(), manytor.py:141-153, at the current pose (also
  * zeroes the coordinates of dead targets, :148).  Result in MT_F_OBS. */

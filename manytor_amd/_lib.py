@@ -314,6 +314,55 @@ ES_INPLACE = 0x1
 ES_UPDATE_ONLY = 0x2
 ES_SHAPE_RANK, ES_SHAPE_RAW = 0, 1
 
+
+class MtPolicyGrad(C.Structure):
+    """struct mt_policy_grad of include/manytor_hip.h: the argument block of mt_policy_grad."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_steps", C.c_int32),
+        ("n_layers", C.c_int32),
+        ("width", C.c_int32 * 2),
+        ("hidden_act", C.c_int32),
+        ("out_act", C.c_int32),
+        ("weight", C.c_void_p * 3),
+        ("bias", C.c_void_p * 3),
+        ("out_scale", C.c_float),
+        ("sigma", C.c_float * MT_MAX_DOF),
+        ("flags", C.c_uint32),
+        ("obs", C.c_void_p),
+        ("obs_ld", C.c_int64),
+        ("action", C.c_void_p),
+        ("act_ld", C.c_int64),
+        ("coef", C.c_void_p),
+        ("coef_ld", C.c_int64),
+        ("scale", C.c_float),
+        ("grad_out", C.c_void_p),
+        ("loss_out", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_size_t),
+        ("reserved", C.c_uint64),
+    ]
+
+
+class MtRewardToGo(C.Structure):
+    """struct mt_reward_to_go of include/manytor_hip.h: the argument block of mt_reward_to_go."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_steps", C.c_int32),
+        ("reward_log", C.c_void_p),
+        ("done_log", C.c_void_p),
+        ("log_ld", C.c_int64),
+        ("gamma", C.c_float),
+        ("baseline", C.c_float),
+        ("out", C.c_void_p),
+        ("out_ld", C.c_int64),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+RTG_MASK_AFTER_DONE = 0x1
+
 _HANDLE = C.c_void_p
 
 # name -> (restype, argtypes); exactly the prototypes of include/manytor_hip.h
@@ -351,6 +400,9 @@ PROTOTYPES = {
     "mt_es_sample": (C.c_int, [_HANDLE, C.POINTER(MtEsSample)]),
     "mt_rollout_population": (C.c_int, [_HANDLE, C.POINTER(MtPopulation)]),
     "mt_es": (C.c_int, [_HANDLE, C.POINTER(MtEs)]),
+    "mt_policy_grad": (C.c_int, [_HANDLE, C.POINTER(MtPolicyGrad)]),
+    "mt_policy_grad_workspace": (C.c_size_t, [_HANDLE, C.c_int, C.POINTER(C.c_int32), C.c_uint32, C.c_int]),
+    "mt_reward_to_go": (C.c_int, [_HANDLE, C.POINTER(MtRewardToGo)]),
     "mt_observe": (C.c_int, [_HANDLE]),
     "mt_check_done": (C.c_int, [_HANDLE]),
     "mt_get": (C.c_int, [_HANDLE, C.c_int, C.c_void_p, C.c_int64, C.c_int]),

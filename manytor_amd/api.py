@@ -340,6 +340,12 @@ class Multienv:
             self._step_idx += int(steps)
         return res
 
+    def policy_gradient(self, layers_or_theta, obs, actions, coef, **kw):
+        """scale * sum over the logged samples of coef * d log pi(action | obs) / d theta, as one flat vector in
+        flatten_policy's layout (StepEngine.policy_grad, which documents the keywords; StepEngine.reward_to_go makes the
+        usual `coef` from run-time logs).  Nothing of the envs is read or moved."""
+        return self._engine.policy_grad(layers_or_theta, obs, actions, coef, **kw)
+
     def close(self):
         self._engine.close()
 

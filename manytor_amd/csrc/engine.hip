@@ -2525,6 +2525,193 @@ int mt_es(mt_handle h, const struct mt_es* s) {
   return check_launch(h, "es_update_kernel");
 }
 
+// ---- mt_policy_grad, mt_reward_to_go -----------------------------------------------------------------------------------
+// The shape of a policy on this handle: per-layer fan-in / fan-out, the layers' offsets in the flat vector, and P.
+struct PolicyLayout {
+  int32_t n_in[3], n_out[3];
+  int64_t off[3], P;
+  int widest;
+};
+static bool policy_layout(const mt_engine* h, int L, const int32_t width[2], uint32_t flags, PolicyLayout* s) {
+  if (L < 1 || L > MT_POLICY_MAX_LAYERS || (flags & ~(uint32_t)MT_POLICY_SEE_POSE)) return false;
+  int n_in = 3 * h->K + ((flags & MT_POLICY_SEE_POSE) ? h->D : 0);
+  s->P = 0;
+  s->widest = 0;
+  for (int l = 0; l < L; ++l) {
+    if (l + 1 < L && (width[l] < 1 || width[l] > MT_POLICY_MAX_WIDTH)) return false;
+    const int n_out = (l + 1 < L) ? width[l] : h->D;
+    if (l + 1 < L) s->widest = std::max(s->widest, n_out);
+    s->n_in[l] = n_in;
+    s->n_out[l] = n_out;
+    s->off[l] = s->P;
+    s->P += (int64_t)n_out * n_in + n_out;
+    n_in = n_out;
+  }
+  return true;
+}
+// policy_grad_kernel's grid: a block per tile of kBlock envs of one step, at most two blocks per compute unit
+static int64_t policy_grad_blocks(mt_handle h, int T) {
+  if (h->cu_count <= 0) {
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->cfg.device) != hipSuccess || cus <= 0) {
+      (void)hipGetLastError();
+      cus = 256;
+    }
+    h->cu_count = cus;
+  }
+  const int64_t tiles = (int64_t)T * ((h->n + kBlock - 1) / kBlock);
+  return std::min<int64_t>(tiles, 2 * (int64_t)h->cu_count);
+}
+size_t mt_policy_grad_workspace(mt_handle h, int n_layers, const int32_t width[2], uint32_t flags, int n_steps) {
+  PolicyLayout s;
+  const int32_t none[2] = {0, 0};
+  if (!h || n_steps <= 0 || n_steps > 65535 || !policy_layout(h, n_layers, width ? width : none, flags, &s)) return 0;
+  return (size_t)policy_grad_blocks(h, n_steps) * (size_t)(s.P + 1) * sizeof(float);
+}
+static bool bytes_overlap(const void* p, size_t np, const void* q, size_t nq) {
+  const uintptr_t a0 = (uintptr_t)p, a1 = a0 + np, b0 = (uintptr_t)q, b1 = b0 + nq;
+  return p && q && np && nq && a0 < b1 && b0 < a1;
+}
+
+int mt_policy_grad(mt_handle h, const struct mt_policy_grad* p) {
+  MT_REQUIRE(h, p != nullptr, "policy_grad is NULL");  // (the struct first: its size is checked with or without a handle)
+  MT_REQUIRE(h, p->struct_size == (int32_t)sizeof(struct mt_policy_grad), "mt_policy_grad.struct_size does not match this library");
+  // what needs no handle: the scalars
+  MT_REQUIRE(h, p->reserved == 0, "mt_policy_grad.reserved must be 0");
+  MT_REQUIRE(h, (p->flags & ~(uint32_t)MT_POLICY_SEE_POSE) == 0, "mt_policy_grad.flags: only MT_POLICY_SEE_POSE is read");
+  MT_REQUIRE(h, p->n_steps >= 0 && p->n_steps <= 65535, "mt_policy_grad.n_steps must be 0..65535");
+  const int L = p->n_layers;
+  MT_REQUIRE(h, L >= 1 && L <= MT_POLICY_MAX_LAYERS, "mt_policy_grad.n_layers must be 1.." + std::to_string(MT_POLICY_MAX_LAYERS));
+  for (int l = 0; l + 1 < L; ++l)
+    MT_REQUIRE(h, p->width[l] >= 1 && p->width[l] <= MT_POLICY_MAX_WIDTH,
+               "mt_policy_grad.width[" + std::to_string(l) + "] must be 1.." + std::to_string(MT_POLICY_MAX_WIDTH));
+  MT_REQUIRE(h, L == 1 || p->hidden_act == MT_ACT_TANH || p->hidden_act == MT_ACT_RELU, "mt_policy_grad.hidden_act must be MT_ACT_TANH or MT_ACT_RELU");
+  MT_REQUIRE(h, p->out_act == MT_ACT_TANH || p->out_act == MT_ACT_IDENTITY, "mt_policy_grad.out_act must be MT_ACT_TANH or MT_ACT_IDENTITY");
+  // (bit patterns: the build is -ffinite-math-only)
+  MT_REQUIRE(h, first_unusable(&p->out_scale, 1, kMaxFiniteBits) < 0, "mt_policy_grad.out_scale must be finite");
+  MT_REQUIRE(h, first_unusable(&p->scale, 1, kMaxFiniteBits) < 0, "mt_policy_grad.scale must be finite");
+  for (int j = 0; j < MT_MAX_DOF; ++j)  // (every handle has at least one joint; entries past D are not read)
+    MT_REQUIRE(h, first_unusable(&p->sigma[j], 1, kMaxFiniteBits) < 0 && (j == 0 ? p->sigma[j] > 0.f : p->sigma[j] >= 0.f),
+               "mt_policy_grad.sigma[" + std::to_string(j) + "] must be finite and > 0");
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  for (int j = 0; j < h->D; ++j)
+    MT_REQUIRE(h, p->sigma[j] > 0.f, "mt_policy_grad.sigma[" + std::to_string(j) + "] must be finite and > 0");
+  PolicyLayout s;
+  MT_REQUIRE(h, policy_layout(h, L, p->width, p->flags, &s), "mt_policy_grad: not a policy shape");
+  const int T = p->n_steps;
+  const int64_t n = h->n, P = s.P;
+  const int IN = s.n_in[0], D = h->D;
+  MT_REQUIRE(h, p->grad_out != nullptr, "mt_policy_grad.grad_out is NULL");
+  const size_t need = T ? (size_t)policy_grad_blocks(h, T) * (size_t)(P + 1) * sizeof(float) : 0;
+  if (T) {
+    for (int l = 0; l < L; ++l)
+      MT_REQUIRE(h, p->weight[l] != nullptr && p->bias[l] != nullptr, "mt_policy_grad.weight / bias [" + std::to_string(l) + "] is NULL");
+    MT_REQUIRE(h, p->obs != nullptr && p->action != nullptr && p->coef != nullptr, "mt_policy_grad.obs / action / coef is NULL");
+    MT_REQUIRE(h, p->obs_ld >= n, "mt_policy_grad.obs_ld is smaller than n_envs");
+    MT_REQUIRE(h, p->act_ld >= n, "mt_policy_grad.act_ld is smaller than n_envs");
+    MT_REQUIRE(h, p->coef_ld >= n, "mt_policy_grad.coef_ld is smaller than n_envs");
+    MT_REQUIRE(h, p->workspace != nullptr && ((uintptr_t)p->workspace & 3u) == 0, "mt_policy_grad.workspace is NULL or not 4-byte aligned");
+    MT_REQUIRE(h, p->workspace_bytes >= need,
+               "mt_policy_grad.workspace_bytes is smaller than mt_policy_grad_workspace() = " + std::to_string(need));
+    // the outputs against the inputs and against each other
+    const void* out[3] = {p->grad_out, p->loss_out, p->workspace};
+    const size_t out_bytes[3] = {(size_t)P * 4, p->loss_out ? (size_t)4 : 0, need};
+    const char* out_name[3] = {"grad_out", "loss_out", "workspace"};
+    for (int a = 0; a < 3; ++a) {
+      const std::string msg = std::string("mt_policy_grad.") + out_name[a] + " overlaps ";
+      for (int l = 0; l < L; ++l)
+        MT_REQUIRE(h, !bytes_overlap(out[a], out_bytes[a], p->weight[l], (size_t)s.n_out[l] * s.n_in[l] * 4) &&
+                          !bytes_overlap(out[a], out_bytes[a], p->bias[l], (size_t)s.n_out[l] * 4),
+                   msg + "weight / bias [" + std::to_string(l) + "]");
+      MT_REQUIRE(h, !bytes_overlap(out[a], out_bytes[a], p->obs, (size_t)(((int64_t)T * IN - 1) * p->obs_ld + n) * 4), msg + "obs");
+      MT_REQUIRE(h, !bytes_overlap(out[a], out_bytes[a], p->action, (size_t)(((int64_t)T * D - 1) * p->act_ld + n) * 4), msg + "action");
+      MT_REQUIRE(h, !bytes_overlap(out[a], out_bytes[a], p->coef, (size_t)(((int64_t)T - 1) * p->coef_ld + n) * 4), msg + "coef");
+      for (int b = a + 1; b < 3; ++b)
+        MT_REQUIRE(h, !bytes_overlap(out[a], out_bytes[a], out[b], out_bytes[b]), msg + out_name[b]);
+    }
+  }
+  MT_ENTER(h);
+  PolicyGradArgs r{};
+  for (int l = 0; l < L; ++l) {
+    r.w[l] = p->weight[l];
+    r.b[l] = p->bias[l];
+    r.n_in[l] = s.n_in[l];
+    r.n_out[l] = s.n_out[l];
+    r.off[l] = s.off[l];
+  }
+  r.L = L;
+  r.T = T;
+  r.K = h->K;
+  r.D = D;
+  r.hidden_act = p->hidden_act;
+  r.out_act = p->out_act;
+  r.out_scale = p->out_scale;
+  for (int j = 0; j < D; ++j) r.inv_var[j] = (float)(1.0 / ((double)p->sigma[j] * (double)p->sigma[j]));
+  r.see_pose = (p->flags & MT_POLICY_SEE_POSE) ? 1u : 0u;
+  r.obs = p->obs;
+  r.obs_ld = p->obs_ld;
+  r.action = p->action;
+  r.act_ld = p->act_ld;
+  r.coef = p->coef;
+  r.coef_ld = p->coef_ld;
+  r.n = n;
+  r.tiles_per_step = (n + kBlock - 1) / kBlock;
+  r.tiles = (int64_t)T * r.tiles_per_step;
+  r.P = P;
+  r.partials = static_cast<float*>(p->workspace);
+  r.blocks = T ? (int32_t)policy_grad_blocks(h, T) : 0;
+  r.scale = p->scale;
+  r.grad = p->grad_out;
+  r.loss = p->loss_out;
+  if (T) {
+    // the smallest compiled (extent, chunks of x) that holds the policy: kernels.h PolicyGradShape
+    if (s.widest <= 32)
+      hipLaunchKernelGGL((policy_grad_kernel<32, 4>), dim3((unsigned)r.blocks), dim3(kBlock), 0, h->stream, r);
+    else if (IN <= 64)
+      hipLaunchKernelGGL((policy_grad_kernel<64, 1>), dim3((unsigned)r.blocks), dim3(kBlock), 0, h->stream, r);
+    else
+      hipLaunchKernelGGL((policy_grad_kernel<64, 2>), dim3((unsigned)r.blocks), dim3(kBlock), 0, h->stream, r);
+    int rc = check_launch(h, "policy_grad_kernel");
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(policy_grad_reduce_kernel, grid_for(P + 1), dim3(kBlock), 0, h->stream, r);
+  return check_launch(h, "policy_grad_reduce_kernel");
+}
+
+int mt_reward_to_go(mt_handle h, const struct mt_reward_to_go* s) {
+  MT_REQUIRE(h, s != nullptr, "reward_to_go is NULL");  // (the struct first: its size is checked with or without a handle)
+  MT_REQUIRE(h, s->struct_size == (int32_t)sizeof(struct mt_reward_to_go), "mt_reward_to_go.struct_size does not match this library");
+  MT_REQUIRE(h, s->reserved == 0, "mt_reward_to_go.reserved must be 0");
+  MT_REQUIRE(h, (s->flags & ~(uint32_t)MT_RTG_MASK_AFTER_DONE) == 0, "mt_reward_to_go.flags: unknown MT_RTG_* flag");
+  MT_REQUIRE(h, s->n_steps >= 0 && s->n_steps <= 65535, "mt_reward_to_go.n_steps must be 0..65535");
+  // (bit patterns: the build is -ffinite-math-only)
+  MT_REQUIRE(h, first_unusable(&s->gamma, 1, kMaxFiniteBits) < 0 && s->gamma >= 0.f && s->gamma <= 1.f, "mt_reward_to_go.gamma must be in [0, 1]");
+  MT_REQUIRE(h, first_unusable(&s->baseline, 1, kMaxFiniteBits) < 0, "mt_reward_to_go.baseline must be finite");
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  if (s->n_steps == 0) return MT_OK;
+  MT_REQUIRE(h, s->reward_log != nullptr && s->done_log != nullptr && s->out != nullptr, "mt_reward_to_go.reward_log / done_log / out is NULL");
+  MT_REQUIRE(h, s->log_ld >= h->n, "mt_reward_to_go.log_ld is smaller than n_envs");
+  MT_REQUIRE(h, s->out_ld >= h->n, "mt_reward_to_go.out_ld is smaller than n_envs");
+  const size_t log_bytes = (size_t)(((int64_t)s->n_steps - 1) * s->log_ld + h->n);
+  const size_t out_bytes = (size_t)(((int64_t)s->n_steps - 1) * s->out_ld + h->n) * 4;
+  MT_REQUIRE(h, !bytes_overlap(s->out, out_bytes, s->reward_log, log_bytes) && !bytes_overlap(s->out, out_bytes, s->done_log, log_bytes),
+             "mt_reward_to_go.out overlaps reward_log / done_log");
+  MT_ENTER(h);
+  RewardToGoArgs r{};
+  r.reward = s->reward_log;
+  r.done = s->done_log;
+  r.log_ld = s->log_ld;
+  r.out = s->out;
+  r.out_ld = s->out_ld;
+  r.n = h->n;
+  r.T = s->n_steps;
+  r.gamma = s->gamma;
+  r.baseline = s->baseline;
+  r.mask_after_done = (s->flags & MT_RTG_MASK_AFTER_DONE) ? 1u : 0u;
+  hipLaunchKernelGGL(reward_to_go_kernel, grid_for(h->n), dim3(kBlock), 0, h->stream, r);
+  return check_launch(h, "reward_to_go_kernel");
+}
+
 int mt_shoot(mt_handle h, const struct mt_shoot* s) {
   MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
   MT_REQUIRE(h, s != nullptr, "shoot is NULL");

@@ -132,6 +132,7 @@ struct mt_engine {
   bool gather_pending = false;
   bool gather_inplace = false;  // the pending exchange reads an arena row directly (mt_gather_returns_begin_inplace): resets wait for it
   float last_gather_ms = 0.f;  // device time of the last exchange that was waited for (mt_gather_returns_wait / mt_sync)
+  int cu_count = 0;  // the device's compute units, asked once by mt_policy_grad (its grid and workspace are sized by it)
   std::string err;
   std::string kernel_name;  // mt_step_kernel_name
 };

@@ -2956,6 +2956,392 @@ __global__ __launch_bounds__(kBlock) void es_update_kernel(const EsArgs r) {
 }
 
 // ---------------------------------------------------------------------------
+// The weighted log-likelihood gradient of the MLP policy (mt_policy_grad) and the reward-to-go that usually weights it
+// (mt_reward_to_go).  Neither depends on the DH table nor touches a handle's state.
+//
+// policy_grad_kernel<W>: one sample (t, i) per lane, a block per tile of kBlock consecutive envs of one step; the grid is
+// bounded and block b takes tiles b, b + gridDim.x, ... in that order, its sums kept in registers across them.
+//   forward   policy_feed / policy_bias / policy_finish / policy_hidden / policy_dot as rollout_policy_kernel calls them:
+//             the same fmaf chains, so the same mu bit for bit.  x is streamed from obs (never live as a whole); the hidden
+//             vectors stay in registers for the backward pass.
+//   backward  delta_L = c (a - mu) / sigma^2 out_scale out_act';  delta_l = (W_l+1^T delta_l+1) * act'(h_l): the transposed
+//             product walks the rows o of W_l+1 (scalar loads of eight, the straddling block element by element, as
+//             policy_dot) and takes delta_o from the front of its array, which is ROTATED by eight per block of rows: no
+//             register array is indexed dynamically.
+//   reduction dW_l[o][k] = sum over samples of delta_l[o] h_l[k], db_l[o] = sum of delta_l[o]: per layer, the four waves
+//             of the block put their 64 samples' delta and h into LDS one after the other (sample-major images) and ALL
+//             256 threads add that wave's samples, in sample order, to the (W / 16)^2 outputs each of them owns (thread
+//             (to, tk) = (tid / 16, tid % 16): rows to W/16 .., columns tk W/16 .. of every W-column chunk of the input).
+//             Plain VALU fmaf over LDS broadcast reads; the matrix cores are not used.
+//   skipped   a lane whose sample is skipped (c == 0, an unusable a_j, i >= n_envs) loads neither x nor a and runs with
+//             x = 0, a = 0, c = 0: every delta is then +-0, and adds nothing.
+// Each block writes its sums to its row of the (blocks, P + 1) partials (word P: the loss); policy_grad_reduce_kernel adds
+// the rows in ascending block order and applies scale once.
+// ---------------------------------------------------------------------------
+struct PolicyGradArgs {
+  const float* w[3];
+  const float* b[3];
+  int32_t n_in[3], n_out[3];  // per layer, as PolicyArgs
+  int64_t off[3];             // layer l's W in the flat gradient; its bias follows the matrix
+  int32_t L, T, K, D;
+  int32_t hidden_act, out_act;
+  float out_scale;
+  float inv_var[MT_MAX_DOF];  // the fp32 nearest to 1 / sigma_j^2
+  uint32_t see_pose;
+  const float* obs;  // [T * IN][obs_ld]
+  int64_t obs_ld;
+  const float* action;  // [T * D][act_ld]
+  int64_t act_ld;
+  const float* coef;  // [T][coef_ld]
+  int64_t coef_ld;
+  int64_t n;                      // envs
+  int64_t tiles_per_step, tiles;  // tiles = T * tiles_per_step
+  int64_t P;
+  float* partials;  // [blocks][P + 1]
+  int32_t blocks;
+  float scale;
+  float* grad;  // [P]
+  float* loss;  // [1] or NULL
+};
+
+constexpr int kPolicyGradMaxIn = 3 * MT_MAX_TARGETS + MT_MAX_DOF;  // 104
+constexpr int kPolicyGradOutCols = 128;  // the output layer's tile: 8 rows x 32 threads x 4 columns
+static_assert(kPolicyGradOutCols >= kPolicyGradMaxIn && MT_MAX_DOF <= 8, "the output layer's gradient fits its tile");
+// W: the extent of the hidden register arrays; NCH0: the W-column chunks of x a hidden first layer's gradient is kept in
+// (the host picks the smallest compiled pair that holds the policy: NCH0 * W >= IN)
+template <int W, int NCH0>
+struct PolicyGradShape {
+  static constexpr int TO = W / 16;                 // a thread's outputs of a hidden layer: TO rows x TO columns per chunk
+  static constexpr int AP = W + 4;                  // pitch of the delta image [64][AP]
+  static constexpr int BP = NCH0 * W + 4;           // pitch of the input image [64][BP]
+  static constexpr int kWords = 64 * (AP + BP);
+  static_assert(kWords >= kBlock, "the loss is summed through the same words");
+};
+template <int W, int NCH>
+struct PolicyGradTile {  // what one thread owns of a hidden layer's gradient
+  float w[NCH][W / 16][W / 16];
+  float b[W / 16];
+};
+struct PolicyGradOutTile {  // ... and of the output layer's: row tid / 32, columns 4 (tid % 32) ..
+  float w[4];
+  float b;
+};
+
+__device__ __forceinline__ float policy_act_slope(int act, float h) {  // from the forward VALUE h (act is wave-uniform)
+  if (act == MT_ACT_TANH) {
+    const float hh = h * h;
+    return 1.f - hh;
+  }
+  if (act == MT_ACT_RELU) return h > 0.f ? 1.f : 0.f;
+  return 1.f;
+}
+
+// out[k] = sum over o < n_out of W[o][k] delta[o], k < n_in (0 past it); delta has the static extent ND >= n_out
+template <int ND, int W>
+__device__ __forceinline__ void policy_backprop(weight_ptr w, int n_in, int n_out, float (&delta)[ND], float (&out)[W]) {
+#pragma unroll
+  for (int k = 0; k < W; ++k) out[k] = 0.f;
+#pragma unroll 1
+  for (int o0 = 0; o0 < ND; o0 += 8) {
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      if (o0 + q < n_out) {
+        const weight_ptr row = w + (int64_t)(o0 + q) * n_in;
+        const float d = delta[q];
+#pragma unroll
+        for (int k0 = 0; k0 < W; k0 += 8) {
+          if (k0 + 8 <= n_in) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) out[k0 + e] = __builtin_fmaf(row[k0 + e], d, out[k0 + e]);
+          } else if (k0 < n_in) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+              if (k0 + e < n_in) out[k0 + e] = __builtin_fmaf(row[k0 + e], d, out[k0 + e]);
+          }
+        }
+      }
+    }
+    if constexpr (ND > 8) {  // the next eight to the front; after ND / 8 turns the array is as it was
+      float head[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) head[q] = delta[q];
+#pragma unroll
+      for (int o = 0; o < ND - 8; ++o) delta[o] = delta[o + 8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) delta[ND - 8 + q] = head[q];
+    }
+  }
+}
+
+// a lane's vector into its row of a sample-major LDS image
+template <int N>
+__device__ __forceinline__ void policy_grad_put(float* row, const float (&v)[N]) {
+#pragma unroll
+  for (int o = 0; o < N; ++o) row[o] = v[o];
+}
+
+// the 64 samples of the images, in sample order, into the outputs this thread owns
+template <int AP, int BP, int W, int NCH>
+__device__ __forceinline__ void policy_grad_accumulate(PolicyGradTile<W, NCH>& g, const float* A, const float* B, int n_in, int n_out) {
+  constexpr int TO = W / 16;
+  const int to = threadIdx.x >> 4, tk = threadIdx.x & 15;
+  if (TO * to < n_out) {
+    const float* a = A + TO * to;
+    const float* b = B + TO * tk;
+#pragma unroll 2
+    for (int s = 0; s < 64; ++s) {
+      float d[TO];
+#pragma unroll
+      for (int i = 0; i < TO; ++i) d[i] = a[s * AP + i];
+#pragma unroll
+      for (int i = 0; i < TO; ++i) g.b[i] = g.b[i] + d[i];
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch) {
+        if (ch * W < n_in) {
+          float x[TO];
+#pragma unroll
+          for (int j = 0; j < TO; ++j) x[j] = b[s * BP + ch * W + j];
+#pragma unroll
+          for (int i = 0; i < TO; ++i)
+#pragma unroll
+            for (int j = 0; j < TO; ++j) g.w[ch][i][j] = __builtin_fmaf(d[i], x[j], g.w[ch][i][j]);
+        }
+      }
+    }
+  }
+}
+template <int AP, int BP>
+__device__ __forceinline__ void policy_grad_accumulate(PolicyGradOutTile& g, const float* A, const float* B, int n_in, int n_out) {
+  const int to = threadIdx.x >> 5, tk = threadIdx.x & 31;
+  if (to < n_out && 4 * tk < n_in) {  // (columns up to the next multiple of four: the images are written that far)
+    const float* a = A + to;
+    const float* b = B + 4 * tk;
+#pragma unroll 2
+    for (int s = 0; s < 64; ++s) {
+      const float d = a[s * AP];
+      g.b = g.b + d;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) g.w[j] = __builtin_fmaf(d, b[s * BP + j], g.w[j]);
+    }
+  }
+}
+
+template <int W, int NCH>
+__device__ __forceinline__ void policy_grad_store(const PolicyGradTile<W, NCH>& g, float* part, int n_in, int n_out) {
+  constexpr int TO = W / 16;
+  const int to = threadIdx.x >> 4, tk = threadIdx.x & 15;
+#pragma unroll
+  for (int i = 0; i < TO; ++i) {
+    const int o = TO * to + i;
+    if (o < n_out) {
+#pragma unroll
+      for (int ch = 0; ch < NCH; ++ch)
+#pragma unroll
+        for (int j = 0; j < TO; ++j) {
+          const int k = ch * W + TO * tk + j;
+          if (k < n_in) part[(int64_t)o * n_in + k] = g.w[ch][i][j];
+        }
+      if (tk == 0) part[(int64_t)n_out * n_in + o] = g.b[i];
+    }
+  }
+}
+__device__ __forceinline__ void policy_grad_store(const PolicyGradOutTile& g, float* part, int n_in, int n_out) {
+  const int to = threadIdx.x >> 5, tk = threadIdx.x & 31;
+  if (to < n_out) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (4 * tk + j < n_in) part[(int64_t)to * n_in + 4 * tk + j] = g.w[j];
+    if (tk == 0) part[(int64_t)n_out * n_in + to] = g.b;
+  }
+}
+
+template <int W, int NCH0>
+__global__ __launch_bounds__(kBlock) void policy_grad_kernel(const PolicyGradArgs r) {
+  using S = PolicyGradShape<W, NCH0>;
+  __shared__ __attribute__((aligned(16))) float img[S::kWords];
+  float* const A = img;
+  float* const B = img + 64 * S::AP;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int L = r.L, IN = r.n_in[0], D = r.D;
+  const weight_ptr w0 = as_weights(r.w[0]), b0 = as_weights(r.b[0]);
+  const weight_ptr wl = as_weights(r.w[L - 1]), bl = as_weights(r.b[L - 1]);  // the output layer
+  float* const arow = A + lane * S::AP;
+  float* const brow = B + lane * S::BP;
+
+  PolicyGradOutTile gout{};           // the output layer (the first one when L == 1)
+  PolicyGradTile<W, NCH0> gh0{};      // hidden layer 0: L >= 2
+  PolicyGradTile<W, 1> gh1{};         // hidden layer 1: L == 3
+  float loss = 0.f;
+
+  for (int64_t tile = blockIdx.x; tile < r.tiles; tile += gridDim.x) {  // (block-uniform: every thread meets every barrier)
+    const int64_t t = tile / r.tiles_per_step;
+    const int64_t i = (tile - t * r.tiles_per_step) * kBlock + threadIdx.x;
+    bool active = i < r.n;
+    float c = 0.f, a[MT_MAX_DOF];
+    if (active) c = r.coef[t * r.coef_ld + i];
+    active = active && c != 0.f;
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < MT_MAX_DOF; ++j) {
+      a[j] = 0.f;
+      if (active && j < D) a[j] = r.action[(t * D + j) * r.act_ld + i];
+      bad |= unusable_angle(a[j]);
+    }
+    active = active && !bad;
+    if (!active) {
+      c = 0.f;
+#pragma unroll
+      for (int j = 0; j < MT_MAX_DOF; ++j) a[j] = 0.f;
+    }
+    const float* xcol = r.obs + t * IN * r.obs_ld + i;  // x_k = xcol[k obs_ld], read by active lanes only
+    auto first_layer = [&](auto& acc, int n_out) {
+      policy_bias(acc, b0, n_out);
+      for (int k = 0; k < r.K; ++k) {
+        float tri[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) tri[q] = active ? xcol[(int64_t)(3 * k + q) * r.obs_ld] : 0.f;
+        policy_feed(acc, w0, IN, n_out, 3 * k, tri);
+      }
+      if (r.see_pose) {
+        for (int j = 0; j < D; ++j) {
+          const float xj[1] = {active ? xcol[(int64_t)(3 * r.K + j) * r.obs_ld] : 0.f};
+          policy_feed(acc, w0, IN, n_out, 3 * r.K + j, xj);
+        }
+      }
+    };
+    // the images of one layer, wave after wave, into the outputs the threads own
+    auto reduce = [&](auto& g, const auto& delta, auto&& put_input, int n_in, int n_out) {
+#pragma unroll 1
+      for (int p = 0; p < kBlock / 64; ++p) {
+        __syncthreads();
+        if (wave == p) {
+          policy_grad_put(arow, delta);
+          put_input();
+        }
+        __syncthreads();
+        policy_grad_accumulate<S::AP, S::BP>(g, A, B, n_in, n_out);
+      }
+    };
+    auto put_x = [&]() {  // with zeros up to the end of the last W-column chunk that holds an input
+#pragma unroll 1
+      for (int k = 0; k < NCH0 * W && (k / W) * W < IN; ++k)
+        brow[k] = (active && k < IN) ? xcol[(int64_t)k * r.obs_ld] : 0.f;
+    };
+
+    float y[MT_MAX_DOF], h0[W], h1[W];
+    if (L == 1) {
+      first_layer(y, D);
+    } else {
+      first_layer(h0, r.n_out[0]);
+      policy_finish(h0, r.hidden_act, r.n_out[0]);
+      if (L == 2) {
+#pragma unroll
+        for (int j = 0; j < MT_MAX_DOF; ++j) y[j] = j < D ? policy_dot<W>(wl + (int64_t)j * r.n_in[1], bl[j], r.n_in[1], h0) : 0.f;
+      } else {
+#pragma unroll
+        for (int o = 0; o < W; ++o) h1[o] = 0.f;
+        policy_hidden<W>(as_weights(r.w[1]), as_weights(r.b[1]), r.n_in[1], r.n_out[1], r.hidden_act, h0, h1);
+#pragma unroll
+        for (int j = 0; j < MT_MAX_DOF; ++j) y[j] = j < D ? policy_dot<W>(wl + (int64_t)j * r.n_in[2], bl[j], r.n_in[2], h1) : 0.f;
+      }
+    }
+    float dl[MT_MAX_DOF], lp = 0.f;
+#pragma unroll
+    for (int j = 0; j < MT_MAX_DOF; ++j) {
+      dl[j] = 0.f;
+      if (j < D) {
+        const float tj = policy_act(r.out_act, y[j]);
+        const float mu = r.out_scale * tj;
+        const float e = a[j] - mu;
+        const float d = e * r.inv_var[j];
+        lp = __builtin_fmaf(e, d, lp);
+        dl[j] = ((c * d) * r.out_scale) * policy_act_slope(r.out_act, tj);
+      }
+    }
+    loss = __builtin_fmaf(c, -0.5f * lp, loss);
+
+    if (L == 1) {
+      reduce(gout, dl, put_x, IN, D);
+    } else if (L == 2) {
+      reduce(gout, dl, [&]() { policy_grad_put(brow, h0); }, r.n_in[1], D);
+      float d0[W];
+      policy_backprop<MT_MAX_DOF, W>(wl, r.n_in[1], D, dl, d0);
+#pragma unroll
+      for (int k = 0; k < W; ++k) d0[k] = d0[k] * policy_act_slope(r.hidden_act, h0[k]);
+      reduce(gh0, d0, put_x, IN, r.n_out[0]);
+    } else {
+      reduce(gout, dl, [&]() { policy_grad_put(brow, h1); }, r.n_in[2], D);
+      float d1[W];
+      policy_backprop<MT_MAX_DOF, W>(wl, r.n_in[2], D, dl, d1);
+#pragma unroll
+      for (int k = 0; k < W; ++k) d1[k] = d1[k] * policy_act_slope(r.hidden_act, h1[k]);
+      reduce(gh1, d1, [&]() { policy_grad_put(brow, h0); }, r.n_in[1], r.n_out[1]);
+      float d0[W];
+      policy_backprop<W, W>(as_weights(r.w[1]), r.n_in[1], r.n_out[1], d1, d0);
+#pragma unroll
+      for (int k = 0; k < W; ++k) d0[k] = d0[k] * policy_act_slope(r.hidden_act, h0[k]);
+      reduce(gh0, d0, put_x, IN, r.n_out[0]);
+    }
+  }
+
+  float* part = r.partials + (int64_t)blockIdx.x * (r.P + 1);
+  policy_grad_store(gout, part + r.off[L - 1], r.n_in[L - 1], D);
+  if (L >= 2) policy_grad_store(gh0, part + r.off[0], IN, r.n_out[0]);
+  if (L == 3) policy_grad_store(gh1, part + r.off[1], r.n_in[1], r.n_out[1]);
+  __syncthreads();
+  img[threadIdx.x] = loss;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int q = 0; q < kBlock; ++q) s = s + img[q];
+    part[r.P] = s;
+  }
+}
+
+// grad[i] = scale * (partials[0][i] + partials[1][i] + ...), ascending; word P is the loss
+__global__ __launch_bounds__(kBlock) void policy_grad_reduce_kernel(const PolicyGradArgs r) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i > r.P) return;
+  float s = 0.f;
+  for (int b = 0; b < r.blocks; ++b) s = s + r.partials[(int64_t)b * (r.P + 1) + i];
+  s = s * r.scale;
+  if (i < r.P) r.grad[i] = s;
+  else if (r.loss) r.loss[0] = s;
+}
+
+struct RewardToGoArgs {
+  const int8_t* reward;  // [T][log_ld]
+  const uint8_t* done;
+  int64_t log_ld;
+  float* out;  // [T][out_ld]
+  int64_t out_ld;
+  int64_t n;
+  int32_t T;
+  float gamma, baseline;
+  uint32_t mask_after_done;
+};
+// one lane per env, backwards over t: R_t = fmaf(gamma, done_t ? 0 : R_t+1, r_t); steps behind the first done are 0 when masked
+__global__ __launch_bounds__(kBlock) void reward_to_go_kernel(const RewardToGoArgs r) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= r.n) return;
+  int first = r.T;
+  if (r.mask_after_done) {
+    for (int t = r.T - 1; t >= 0; --t)
+      if (r.done[(int64_t)t * r.log_ld + i]) first = t;
+  }
+  float R = 0.f;
+  for (int t = r.T - 1; t >= 0; --t) {
+    float v = 0.f;
+    if (t <= first) {
+      const bool d = r.done[(int64_t)t * r.log_ld + i] != 0;
+      R = __builtin_fmaf(r.gamma, d ? 0.f : R, (float)r.reward[(int64_t)t * r.log_ld + i]);
+      v = R - r.baseline;
+    }
+    r.out[(int64_t)t * r.out_ld + i] = v;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // mt_shoot's evaluation: C candidate tapes per env scored from the SAME resident state, the best one named.  For env i
 // and candidate c, returns[c][i] is what rollout_tape_kernel's dry run writes to return_out[i] for plane c, bit for bit;
 // best[i] is the smallest c whose return is maximal.  Nothing resident is written.

@@ -828,6 +828,143 @@ class StepEngine:
         res["coeff"], res["sums"] = res["coeff"][:m // 2], res["coeff"][m // 2:]
         return res
 
+    # ---- the policy's log-likelihood gradient from rollout_policy's logs ---------------------------------------------------
+    def _log_rows(self, t, name, rows, dtype):
+        """A (T, rows, N) log (rows None: (T, N)) as the library reads it: `dtype`, on this device, unit stride along the
+        envs, whole rows of ld >= N elements between them (a [..., :N] view of a wider buffer is read in place).
+        -> (T, ld)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        shape = (rows, self.n_envs) if rows is not None else (self.n_envs,)
+        if (not _is_torch_tensor(t) or t.dtype != dtype or t.device != dev or t.dim() != len(shape) + 1
+                or tuple(t.shape[1:]) != shape):
+            raise ValueError(f"{name} must be a {dtype} tensor of shape (T, {', '.join(str(v) for v in shape)}) on {dev}")
+        T, n = int(t.shape[0]), self.n_envs
+        st = [int(v) for v in t.stride()]
+        if rows is None:
+            ld = st[0] if T > 1 else n
+            dense = True
+        else:
+            ld = st[1] if rows > 1 else st[0] if T > 1 else n
+            dense = T <= 1 or st[0] == rows * ld
+        if not (dense and ld >= n and (n == 1 or st[-1] == 1)):
+            raise ValueError(f"{name}: envs must be contiguous and the rows a constant ld >= N apart, got strides {tuple(st)}")
+        return T, ld
+
+    def reward_to_go(self, reward_log, done_log, gamma=1.0, baseline=0.0, mask_after_done=False, out=None):
+        """The discounted reward-to-go of rollout_policy's logs (mt_reward_to_go): R_t = r_t + gamma * (0 if done_t else
+        R_t+1), minus `baseline`, as a (T, N) float32 device tensor -- policy_grad's usual `coef`.  mask_after_done=True
+        (logs WITHOUT auto_reset, where an env steps on after its episode ended) writes exactly 0 behind an env's first done:
+        policy_grad skips such samples.  One launch; stream behaviour as rollout_actions."""
+        import torch
+        T, ld = self._log_rows(reward_log, "reward_log", None, torch.int8)
+        T2, ld2 = self._log_rows(done_log, "done_log", None, torch.uint8)
+        if T2 != T or (T > 1 and ld2 != ld):
+            raise ValueError("reward_log and done_log must have the same shape and strides")
+        g = float(np.float32(gamma))
+        if not 0.0 <= g <= 1.0:
+            raise ValueError(f"gamma must be in [0, 1], got {gamma!r}")
+        if not np.isfinite(np.float32(baseline)):
+            raise ValueError(f"baseline must be finite, got {baseline!r}")
+        if out is None:
+            out = torch.empty((T, self.n_envs), dtype=torch.float32, device=reward_log.device)
+        To, out_ld = self._log_rows(out, "out", None, torch.float32)
+        if To != T:
+            raise ValueError(f"out must have T = {T} rows")
+        arg = L.MtRewardToGo()
+        arg.struct_size = C.sizeof(L.MtRewardToGo)
+        arg.n_steps = T
+        arg.reward_log, arg.done_log, arg.log_ld = (reward_log.data_ptr(), done_log.data_ptr(), ld) if T else (None, None, self.n_envs)
+        arg.gamma, arg.baseline = g, float(baseline)
+        arg.out, arg.out_ld = (out.data_ptr() if T else None), out_ld
+        arg.flags = L.RTG_MASK_AFTER_DONE if mask_after_done else 0
+        arg.reserved = 0
+        self._torch_call(self._lib.mt_reward_to_go, C.byref(arg), commits=False)
+        return out
+
+    def policy_grad(self, layers_or_theta, obs, actions, coef, *, sigma, widths=(), hidden="tanh", out="tanh", out_scale=180.0,
+                    see_pose=False, scale=1.0, grad_out=None, loss=False):
+        """grad = scale * sum over samples (t, i) of coef[t, i] * d logp / d theta (mt_policy_grad), logp = -1/2 sum_j
+        ((actions[t, j, i] - mu_j(obs[t, :, i])) / sigma_j)^2, mu the policy's action before noise and clamp -- the
+        REINFORCE direction with coef = reward_to_go(...), behaviour cloning with coef = 1, sigma = 1.  `layers_or_theta`: a
+        list of (weight, bias), a torch.nn.Sequential (both as rollout_policy takes them), or the flat theta of
+        flatten_policy with the hidden `widths`.  obs (T, IN, N), actions (T, D, N), coef (T, N): float32 device tensors
+        as rollout_policy(observations=True, actions=True) returns them, or [..., :N] views of wider buffers.  sigma: a
+        float or D floats, > 0.  A sample with coef == 0 or an unusable action contributes exactly nothing.  Returns grad
+        (P,) float32 in flatten_policy's layout (written into `grad_out` when given), so theta += lr * grad ascends; with
+        loss=True (grad, loss), loss a (1,) tensor holding scale * sum coef * logp.  Deterministic: the same arguments give
+        the same bits.  Two launches, no host wait; the workspace is cached on the engine.  Stream behaviour as
+        rollout_actions; nothing resident is read or written."""
+        import torch
+        for name, v, allowed in (("hidden", hidden, ("tanh", "relu")), ("out", out, ("tanh", "identity"))):
+            if v not in allowed:
+                raise ValueError(f"{name} must be one of {allowed}, got {v!r}")
+        dev = torch.device("cuda", self.device)
+        d = self.dof
+        if _is_torch_tensor(layers_or_theta):
+            p = self.policy_size(widths, see_pose)
+            pairs = self.unflatten_policy(self._flat_vector(layers_or_theta, "theta", p), widths, see_pose)
+        else:
+            pairs = self._policy_layers(layers_or_theta, hidden, out)
+        if not 1 <= len(pairs) <= L.POLICY_MAX_LAYERS:
+            raise ValueError(f"a policy has 1..{L.POLICY_MAX_LAYERS} linear layers, got {len(pairs)}")
+        n_in = 3 * self.obj_number + (d if see_pose else 0)
+        arg = L.MtPolicyGrad()
+        keep, fan_in, p = [], n_in, 0
+        for l, (w, b) in enumerate(pairs):
+            w, b = w.detach(), b.detach()
+            fan_out = d if l == len(pairs) - 1 else int(w.shape[0]) if w.dim() == 2 else -1
+            if tuple(w.shape) != (fan_out, fan_in) or tuple(b.shape) != (fan_out,):
+                raise ValueError(f"layer {l}: weight must be ({fan_out if fan_out > 0 else 'out'}, {fan_in}) and bias (out,), got "
+                                 f"{tuple(w.shape)} and {tuple(b.shape)}")
+            if l < len(pairs) - 1 and not 1 <= fan_out <= L.POLICY_MAX_WIDTH:
+                raise ValueError(f"layer {l}: width must be 1..{L.POLICY_MAX_WIDTH}, got {fan_out}")
+            for what, t in (("weight", w), ("bias", b)):
+                if t.dtype != torch.float32 or not t.is_cuda or t.device != dev or not t.is_contiguous():
+                    raise ValueError(f"layer {l}: {what} must be a contiguous float32 tensor on {dev}")
+            keep += [w, b]
+            arg.weight[l], arg.bias[l] = w.data_ptr(), b.data_ptr()
+            if l < len(pairs) - 1:
+                arg.width[l] = fan_out
+            p += fan_out * fan_in + fan_out
+            fan_in = fan_out
+        sig = np.ones(L.MT_MAX_DOF, dtype=np.float32)
+        sig[:d] = np.broadcast_to(np.asarray(sigma, dtype=np.float32), (d,))
+        if not (np.isfinite(sig).all() and (sig > 0).all()):
+            raise ValueError(f"sigma must be finite and > 0, got {sigma!r}")
+        if not (np.isfinite(np.float32(scale)) and np.isfinite(np.float32(out_scale))):
+            raise ValueError("scale and out_scale must be finite")
+        T, obs_ld = self._log_rows(obs, "obs", n_in, torch.float32)
+        Ta, act_ld = self._log_rows(actions, "actions", d, torch.float32)
+        Tc, coef_ld = self._log_rows(coef, "coef", None, torch.float32)
+        if not T == Ta == Tc:
+            raise ValueError(f"obs, actions and coef must have the same number of steps, got {T}, {Ta}, {Tc}")
+        if grad_out is None:
+            grad_out = torch.empty(p, dtype=torch.float32, device=dev)
+        else:
+            self._flat_vector(grad_out, "grad_out", p)
+        loss_t = torch.zeros(1, dtype=torch.float32, device=dev) if loss else None
+        arg.struct_size = C.sizeof(L.MtPolicyGrad)
+        arg.n_steps, arg.n_layers = T, len(pairs)
+        arg.hidden_act, arg.out_act = self._ACTIVATIONS[hidden], self._ACTIVATIONS[out]
+        arg.out_scale, arg.scale = float(out_scale), float(scale)
+        arg.sigma[:] = sig.tolist()
+        arg.flags = L.POLICY_SEE_POSE if see_pose else 0
+        arg.obs, arg.action, arg.coef = (obs.data_ptr(), actions.data_ptr(), coef.data_ptr()) if T else (None, None, None)
+        arg.obs_ld, arg.act_ld, arg.coef_ld = obs_ld, act_ld, coef_ld
+        arg.grad_out = grad_out.data_ptr()
+        arg.loss_out = loss_t.data_ptr() if loss else None
+        need = int(self._lib.mt_policy_grad_workspace(self._h, len(pairs), arg.width, arg.flags, T))
+        ws = getattr(self, "_pg_workspace", None)
+        if need and (ws is None or ws.numel() * 4 < need):
+            ws = self._pg_workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+        arg.workspace = ws.data_ptr() if need else None
+        arg.workspace_bytes = ws.numel() * 4 if need else 0
+        arg.reserved = 0
+        self._torch_call(self._lib.mt_policy_grad, C.byref(arg), commits=False)
+        del keep
+        return (grad_out, loss_t) if loss else grad_out
+
     def shoot(self, plans, *, layout="soa", commit=0, auto_reset=False, seed=0x5EED, all_returns=False, log=False,
               returns=False):
         """A sampling planner's round in one call (mt_shoot): `plans` holds C candidate tapes of T steps per env, (C, T, D, N)
