@@ -41,7 +41,7 @@ extern "C" {
 #define MT_API
 #endif
 
-#define MT_VERSION 460        /* major*10000 + minor*100 + patch */
+#define MT_VERSION 470       /* major*10000 + minor*100 + patch */
 #define MT_MAX_DOF 8
 #define MT_MAX_TARGETS 32
 #define MT_MAX_RETURN_RING 64
@@ -645,6 +645,117 @@ struct mt_reward_to_go {   /* as with mt_cem, the type is always written `struct
   uint32_t reserved;       /* must be 0 */
 };
 MT_API int mt_reward_to_go(mt_handle h, const struct mt_reward_to_go* s);
+
+/* The MLP's forward pass over logged observations: the mean of every sample and, given the logged actions, their
+ * log-probability under the CURRENT weights -- what actor-critic and PPO need next to mt_policy_grad (the value of every
+ * observation with a one-output head; the old and the new log-probability per sample).
+ *
+ * Samples, x and the layers are mt_policy_grad's.  The last layer has n_out outputs: 0 means the handle's D (a policy),
+ * otherwise 1..MT_MAX_DOF (a value head has 1); IN does not depend on it.
+ *   mean_out[t, j, i] = mu_j = out_scale * out_act(y_L)_j: the same helpers in the same order as mt_rollout_policy and
+ *                       mt_policy_grad, so the same fmaf chains and the same bits for the same x.
+ *   logp_out[t, i]    = -0.5f * lp,  lp = 0;  for j = 0 .. n_out-1:  e = a_j - mu_j;  d = e * inv_var_j;  lp = fmaf(e, d, lp)
+ *                       with inv_var_j the fp32 nearest to 1 / sigma_j^2 (formed in double on the host): mt_policy_grad's
+ *                       sequence, so its loss with a one-hot coef and scale = 1 is this number.
+ * A sample with any unusable a_j (NaN, +-inf, beyond +-32768: the rule of every tape) gets logp exactly 0; its mean is
+ * still written, mu does not depend on the action.
+ * Contract.  At least one of mean_out and logp_out; logp_out needs action, and every sigma_j, j < n_out, finite and > 0
+ * (entries behind n_out: finite, >= 0, not read; sigma is not read at all without logp_out).  Everything the host can see
+ * is screened (MT_ERR_INVALID_ARG): the ld's >= n_envs, and an output may overlap neither the weights, obs, action nor the
+ * other output.  Weights cannot be screened: a NaN among them goes through to the mean, as in the rollout.  One launch on
+ * the handle's stream, no allocation, no host wait: legal under stream capture; n_steps == 0 is a no-op.  Nothing
+ * resident is read but the handle's shape.  No word outside the (out, in) matrices, the (out,) vectors and the first
+ * n_envs columns of each row of obs, action, mean_out and logp_out is read or written, whatever the widths (down to 1) and
+ * the ld's. */
+struct mt_policy_eval {    /* as with mt_cem, the type is always written `struct mt_policy_eval` */
+  int32_t struct_size;     /* = sizeof(struct mt_policy_eval), checked */
+  int32_t n_steps;         /* T, 0..65535 */
+  int32_t n_layers;        /* L, as mt_policy */
+  int32_t width[2];
+  int32_t hidden_act;
+  int32_t out_act;
+  const float* weight[3];  /* DEVICE f32, as mt_policy; the last layer is (n_out, in) */
+  const float* bias[3];
+  float out_scale;         /* finite */
+  uint32_t flags;          /* MT_POLICY_SEE_POSE only: it fixes IN */
+  const float* obs;    int64_t obs_ld;    /* DEVICE (T, IN, obs_ld) */
+  int32_t n_out;           /* outputs of the last layer: 0 = the handle's D, else 1..MT_MAX_DOF */
+  float* mean_out;     int64_t mean_ld;   /* DEVICE or NULL: (T, n_out, mean_ld) */
+  const float* action; int64_t act_ld;    /* DEVICE or NULL: (T, n_out, act_ld) */
+  float sigma[MT_MAX_DOF]; /* read with logp_out: finite, > 0 for j < n_out */
+  float* logp_out;     int64_t logp_ld;   /* DEVICE or NULL: (T, logp_ld) */
+  uint64_t reserved;       /* must be 0 */
+};
+MT_API int mt_policy_eval(mt_handle h, const struct mt_policy_eval* p);
+
+/* Generalised advantage estimation over mt_rollout_policy's logs and a critic's values (mt_policy_eval with n_out = 1).
+ * One lane per env runs backwards over t.  With gl the fp32 product gamma * lambda (formed once on the host),
+ * V_T = last_value (0 when NULL), A_T = 0, and for t = T-1 .. 0:
+ *   nv    = done_t ? 0 : V_t+1
+ *   delta = fmaf(gamma, nv, (float)r_t) - V_t          (one fma, one fp32 subtraction)
+ *   A_t   = fmaf(gl, done_t ? 0 : A_t+1, delta)        -> adv_out[t, i]
+ *   ret_t = A_t + V_t                                  (one fp32 add) -> ret_out[t, i], the critic's regression target
+ * weight_out gets 1.0f for every step.  MT_GAE_MASK_AFTER_DONE, for logs without auto-reset: every step behind the env's
+ * FIRST done gets exactly 0 in adv_out, ret_out and weight_out and does not enter the recurrence (mt_reward_to_go's
+ * mask); weight_out is then the `coef` that takes those steps out of mt_value_grad.  With lambda = 1, value all zeros and
+ * last_value NULL adv_out is mt_reward_to_go's output for baseline 0 and the same mask, bit for bit.
+ * gamma and lambda are fp32 in [0, 1].  value and last_value are device memory and cannot be screened.  One launch on the
+ * handle's stream, capturable; reads and writes the first n_envs columns of the T rows only; the outputs may overlap
+ * neither the inputs nor each other; n_steps == 0 is a no-op. */
+#define MT_GAE_MASK_AFTER_DONE 0x1u
+struct mt_gae {            /* as with mt_cem, the type is always written `struct mt_gae` */
+  int32_t struct_size;     /* = sizeof(struct mt_gae), checked */
+  int32_t n_steps;         /* T, 0..65535; 0 is a no-op */
+  const int8_t* reward_log;   /* DEVICE (T, log_ld) */
+  const uint8_t* done_log;    /* DEVICE (T, log_ld) */
+  int64_t log_ld;          /* >= n_envs */
+  const float* value;      int64_t value_ld;    /* DEVICE (T, value_ld): V of the observation step t started from */
+  const float* last_value; /* DEVICE (n_envs,) or NULL (= 0): V of the state behind the last step */
+  float gamma, lambda;     /* each in [0, 1] */
+  float* adv_out;          int64_t adv_ld;      /* DEVICE (T, adv_ld): required */
+  float* ret_out;          int64_t ret_ld;      /* DEVICE (T, ret_ld) or NULL */
+  float* weight_out;       int64_t weight_ld;   /* DEVICE (T, weight_ld) or NULL */
+  uint32_t flags;          /* MT_GAE_* */
+  uint32_t reserved;       /* must be 0 */
+};
+MT_API int mt_gae(mt_handle h, const struct mt_gae* s);
+
+/* The critic's regression gradient, on mt_policy_grad's kernels: the value head is an MLP of the policy's shape whose
+ * last layer has ONE output, V = out_scale * out_act(y), and
+ *   grad = scale * sum_s c_s (R_s - V_s) dV_s / dtheta          (P_v floats, the flat layout W0|b0|W1|b1|W2|b2)
+ *   loss = scale * sum_s c_s (-1/2 (R_s - V_s)^2)
+ * with R = target[t, i] and c = coef[t, i]: 1/2 c (R - V)^2 is mt_policy_grad's log-likelihood with one output, sigma = 1
+ * and the target in the action's place, so theta += lr * grad DESCENDS the squared error (mt_policy_grad's sign).
+ * The tape rule comes with the kernel: a sample with c == 0, or whose target is NaN, +-inf or beyond +-32768, contributes
+ * exactly nothing and its x is never read (mt_gae's weight_out is such a c).  Determinism, the workspace
+ * (mt_value_grad_workspace() bytes), the refusal of aliased buffers and legality under capture are mt_policy_grad's.
+ * With MT_POLICY_SEE_POSE the handle's D must be 3, 4, 6 or 7 (the kernels read x as triples and at most one single word
+ * when the last layer has one output); other joint counts are MT_ERR_UNSUPPORTED. */
+struct mt_value_grad {     /* as with mt_cem, the type is always written `struct mt_value_grad` */
+  int32_t struct_size;     /* = sizeof(struct mt_value_grad), checked */
+  int32_t n_steps;         /* T, 0..65535 */
+  int32_t n_layers;        /* L, as mt_policy; the last layer has one output */
+  int32_t width[2];
+  int32_t hidden_act;
+  int32_t out_act;         /* MT_ACT_IDENTITY or MT_ACT_TANH */
+  const float* weight[3];  /* DEVICE f32, as mt_policy */
+  const float* bias[3];
+  float out_scale;         /* finite */
+  uint32_t flags;          /* MT_POLICY_SEE_POSE only: it fixes IN */
+  const float* obs;    int64_t obs_ld;      /* DEVICE (T, IN, obs_ld) */
+  const float* target; int64_t target_ld;   /* DEVICE (T, target_ld) f32: R, e.g. mt_gae's ret_out */
+  const float* coef;   int64_t coef_ld;     /* DEVICE (T, coef_ld) f32: required */
+  float scale;             /* finite; applied once, at the final conversion */
+  float* grad_out;         /* DEVICE f32 (P_v,): always written */
+  float* loss_out;         /* DEVICE f32 (1,) or NULL */
+  void* workspace;         /* DEVICE, 4-byte aligned; may be NULL when mt_value_grad_workspace() is 0 */
+  size_t workspace_bytes;  /* >= mt_value_grad_workspace() */
+  uint64_t reserved;       /* must be 0 */
+};
+MT_API int mt_value_grad(mt_handle h, const struct mt_value_grad* p);
+/* Bytes of workspace mt_value_grad needs on this handle for a value head of that shape and n_steps (0 for n_steps == 0,
+ * and for arguments mt_value_grad would refuse). */
+MT_API size_t mt_value_grad_workspace(mt_handle h, int n_layers, const int32_t width[2], uint32_t flags, int n_steps);
 
 /* Environment.get_observations(), manytor.py:141-153, at the current pose (also
  * zeroes the coordinates of dead targets, :148).  Result in MT_F_OBS. */

@@ -363,6 +363,88 @@ class MtRewardToGo(C.Structure):
 
 RTG_MASK_AFTER_DONE = 0x1
 
+
+class MtPolicyEval(C.Structure):
+    """struct mt_policy_eval of include/manytor_hip.h: the argument block of mt_policy_eval."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_steps", C.c_int32),
+        ("n_layers", C.c_int32),
+        ("width", C.c_int32 * 2),
+        ("hidden_act", C.c_int32),
+        ("out_act", C.c_int32),
+        ("weight", C.c_void_p * 3),
+        ("bias", C.c_void_p * 3),
+        ("out_scale", C.c_float),
+        ("flags", C.c_uint32),
+        ("obs", C.c_void_p),
+        ("obs_ld", C.c_int64),
+        ("n_out", C.c_int32),
+        ("mean_out", C.c_void_p),
+        ("mean_ld", C.c_int64),
+        ("action", C.c_void_p),
+        ("act_ld", C.c_int64),
+        ("sigma", C.c_float * MT_MAX_DOF),
+        ("logp_out", C.c_void_p),
+        ("logp_ld", C.c_int64),
+        ("reserved", C.c_uint64),
+    ]
+
+
+class MtGae(C.Structure):
+    """struct mt_gae of include/manytor_hip.h: the argument block of mt_gae."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_steps", C.c_int32),
+        ("reward_log", C.c_void_p),
+        ("done_log", C.c_void_p),
+        ("log_ld", C.c_int64),
+        ("value", C.c_void_p),
+        ("value_ld", C.c_int64),
+        ("last_value", C.c_void_p),
+        ("gamma", C.c_float),
+        ("lambda_", C.c_float),
+        ("adv_out", C.c_void_p),
+        ("adv_ld", C.c_int64),
+        ("ret_out", C.c_void_p),
+        ("ret_ld", C.c_int64),
+        ("weight_out", C.c_void_p),
+        ("weight_ld", C.c_int64),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class MtValueGrad(C.Structure):
+    """struct mt_value_grad of include/manytor_hip.h: the argument block of mt_value_grad."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_steps", C.c_int32),
+        ("n_layers", C.c_int32),
+        ("width", C.c_int32 * 2),
+        ("hidden_act", C.c_int32),
+        ("out_act", C.c_int32),
+        ("weight", C.c_void_p * 3),
+        ("bias", C.c_void_p * 3),
+        ("out_scale", C.c_float),
+        ("flags", C.c_uint32),
+        ("obs", C.c_void_p),
+        ("obs_ld", C.c_int64),
+        ("target", C.c_void_p),
+        ("target_ld", C.c_int64),
+        ("coef", C.c_void_p),
+        ("coef_ld", C.c_int64),
+        ("scale", C.c_float),
+        ("grad_out", C.c_void_p),
+        ("loss_out", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_size_t),
+        ("reserved", C.c_uint64),
+    ]
+
+
+GAE_MASK_AFTER_DONE = 0x1
+
 _HANDLE = C.c_void_p
 
 # name -> (restype, argtypes); exactly the prototypes of include/manytor_hip.h
@@ -403,6 +485,10 @@ PROTOTYPES = {
     "mt_policy_grad": (C.c_int, [_HANDLE, C.POINTER(MtPolicyGrad)]),
     "mt_policy_grad_workspace": (C.c_size_t, [_HANDLE, C.c_int, C.POINTER(C.c_int32), C.c_uint32, C.c_int]),
     "mt_reward_to_go": (C.c_int, [_HANDLE, C.POINTER(MtRewardToGo)]),
+    "mt_policy_eval": (C.c_int, [_HANDLE, C.POINTER(MtPolicyEval)]),
+    "mt_gae": (C.c_int, [_HANDLE, C.POINTER(MtGae)]),
+    "mt_value_grad": (C.c_int, [_HANDLE, C.POINTER(MtValueGrad)]),
+    "mt_value_grad_workspace": (C.c_size_t, [_HANDLE, C.c_int, C.POINTER(C.c_int32), C.c_uint32, C.c_int]),
     "mt_observe": (C.c_int, [_HANDLE]),
     "mt_check_done": (C.c_int, [_HANDLE]),
     "mt_get": (C.c_int, [_HANDLE, C.c_int, C.c_void_p, C.c_int64, C.c_int]),

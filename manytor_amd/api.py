@@ -346,6 +346,19 @@ class Multienv:
         usual `coef` from run-time logs).  Nothing of the envs is read or moved."""
         return self._engine.policy_grad(layers_or_theta, obs, actions, coef, **kw)
 
+    def evaluate_policy(self, layers_or_theta, obs, **kw):
+        """The policy's (or, with n_out=1, a value head's) forward pass over logged observations: a dict with `mean` and,
+        given actions= and sigma=, the per-sample `logp` (StepEngine.policy_eval, which documents the keywords)."""
+        return self._engine.policy_eval(layers_or_theta, obs, **kw)
+
+    def advantages(self, reward_log, done_log, values, **kw):
+        """GAE advantages, value targets and sample weights from run-time logs and a critic's values (StepEngine.gae)."""
+        return self._engine.gae(reward_log, done_log, values, **kw)
+
+    def value_gradient(self, layers_or_theta, obs, targets, coef=None, **kw):
+        """The critic's regression gradient, as one flat vector in flatten_policy's layout (StepEngine.value_grad)."""
+        return self._engine.value_grad(layers_or_theta, obs, targets, coef, **kw)
+
     def close(self):
         self._engine.close()
 

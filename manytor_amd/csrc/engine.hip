@@ -2525,21 +2525,22 @@ int mt_es(mt_handle h, const struct mt_es* s) {
   return check_launch(h, "es_update_kernel");
 }
 
-// ---- mt_policy_grad, mt_reward_to_go -----------------------------------------------------------------------------------
+// ---- mt_policy_grad, mt_reward_to_go, mt_policy_eval, mt_gae, mt_value_grad ----------------------------------------------
 // The shape of a policy on this handle: per-layer fan-in / fan-out, the layers' offsets in the flat vector, and P.
+// n_last: the outputs of the last layer, 0 = the handle's D (a value head has 1).
 struct PolicyLayout {
   int32_t n_in[3], n_out[3];
   int64_t off[3], P;
   int widest;
 };
-static bool policy_layout(const mt_engine* h, int L, const int32_t width[2], uint32_t flags, PolicyLayout* s) {
+static bool policy_layout(const mt_engine* h, int L, const int32_t width[2], uint32_t flags, PolicyLayout* s, int n_last = 0) {
   if (L < 1 || L > MT_POLICY_MAX_LAYERS || (flags & ~(uint32_t)MT_POLICY_SEE_POSE)) return false;
   int n_in = 3 * h->K + ((flags & MT_POLICY_SEE_POSE) ? h->D : 0);
   s->P = 0;
   s->widest = 0;
   for (int l = 0; l < L; ++l) {
     if (l + 1 < L && (width[l] < 1 || width[l] > MT_POLICY_MAX_WIDTH)) return false;
-    const int n_out = (l + 1 < L) ? width[l] : h->D;
+    const int n_out = (l + 1 < L) ? width[l] : n_last ? n_last : h->D;
     if (l + 1 < L) s->widest = std::max(s->widest, n_out);
     s->n_in[l] = n_in;
     s->n_out[l] = n_out;
@@ -2562,107 +2563,177 @@ static int64_t policy_grad_blocks(mt_handle h, int T) {
   const int64_t tiles = (int64_t)T * ((h->n + kBlock - 1) / kBlock);
   return std::min<int64_t>(tiles, 2 * (int64_t)h->cu_count);
 }
-size_t mt_policy_grad_workspace(mt_handle h, int n_layers, const int32_t width[2], uint32_t flags, int n_steps) {
+static size_t policy_grad_workspace(mt_handle h, int n_layers, const int32_t width[2], uint32_t flags, int n_steps, int n_last) {
   PolicyLayout s;
   const int32_t none[2] = {0, 0};
-  if (!h || n_steps <= 0 || n_steps > 65535 || !policy_layout(h, n_layers, width ? width : none, flags, &s)) return 0;
+  if (!h || n_steps <= 0 || n_steps > 65535 || !policy_layout(h, n_layers, width ? width : none, flags, &s, n_last)) return 0;
   return (size_t)policy_grad_blocks(h, n_steps) * (size_t)(s.P + 1) * sizeof(float);
+}
+size_t mt_policy_grad_workspace(mt_handle h, int n_layers, const int32_t width[2], uint32_t flags, int n_steps) {
+  return policy_grad_workspace(h, n_layers, width, flags, n_steps, 0);
 }
 static bool bytes_overlap(const void* p, size_t np, const void* q, size_t nq) {
   const uintptr_t a0 = (uintptr_t)p, a1 = a0 + np, b0 = (uintptr_t)q, b1 = b0 + nq;
   return p && q && np && nq && a0 < b1 && b0 < a1;
 }
 
-int mt_policy_grad(mt_handle h, const struct mt_policy_grad* p) {
-  MT_REQUIRE(h, p != nullptr, "policy_grad is NULL");  // (the struct first: its size is checked with or without a handle)
-  MT_REQUIRE(h, p->struct_size == (int32_t)sizeof(struct mt_policy_grad), "mt_policy_grad.struct_size does not match this library");
-  // what needs no handle: the scalars
-  MT_REQUIRE(h, p->reserved == 0, "mt_policy_grad.reserved must be 0");
-  MT_REQUIRE(h, (p->flags & ~(uint32_t)MT_POLICY_SEE_POSE) == 0, "mt_policy_grad.flags: only MT_POLICY_SEE_POSE is read");
-  MT_REQUIRE(h, p->n_steps >= 0 && p->n_steps <= 65535, "mt_policy_grad.n_steps must be 0..65535");
-  const int L = p->n_layers;
-  MT_REQUIRE(h, L >= 1 && L <= MT_POLICY_MAX_LAYERS, "mt_policy_grad.n_layers must be 1.." + std::to_string(MT_POLICY_MAX_LAYERS));
+// What mt_policy_grad, mt_value_grad and mt_policy_eval state about the network alike (`w` is the struct the messages name).
+struct PolicyNet {
+  int32_t n_steps, n_layers;
+  const int32_t* width;
+  int32_t hidden_act, out_act;
+  const float* const* weight;
+  const float* const* bias;
+  float out_scale;
+  uint32_t flags;
+  const float* obs;
+  int64_t obs_ld;
+  uint64_t reserved;
+};
+// (the three structs name these fields alike; a macro, as this is an extern "C" block)
+#define MT_POLICY_NET(p)                                                                                                   \
+  PolicyNet {                                                                                                              \
+    (p)->n_steps, (p)->n_layers, (p)->width, (p)->hidden_act, (p)->out_act, (p)->weight, (p)->bias, (p)->out_scale, (p)->flags, \
+        (p)->obs, (p)->obs_ld, (p)->reserved                                                                               \
+  }
+// ... the scalars of it, which need no handle
+static int policy_net_screen(mt_handle h, const PolicyNet& p, const std::string& w) {
+  MT_REQUIRE(h, p.reserved == 0, w + ".reserved must be 0");
+  MT_REQUIRE(h, (p.flags & ~(uint32_t)MT_POLICY_SEE_POSE) == 0, w + ".flags: only MT_POLICY_SEE_POSE is read");
+  MT_REQUIRE(h, p.n_steps >= 0 && p.n_steps <= 65535, w + ".n_steps must be 0..65535");
+  const int L = p.n_layers;
+  MT_REQUIRE(h, L >= 1 && L <= MT_POLICY_MAX_LAYERS, w + ".n_layers must be 1.." + std::to_string(MT_POLICY_MAX_LAYERS));
   for (int l = 0; l + 1 < L; ++l)
-    MT_REQUIRE(h, p->width[l] >= 1 && p->width[l] <= MT_POLICY_MAX_WIDTH,
-               "mt_policy_grad.width[" + std::to_string(l) + "] must be 1.." + std::to_string(MT_POLICY_MAX_WIDTH));
-  MT_REQUIRE(h, L == 1 || p->hidden_act == MT_ACT_TANH || p->hidden_act == MT_ACT_RELU, "mt_policy_grad.hidden_act must be MT_ACT_TANH or MT_ACT_RELU");
-  MT_REQUIRE(h, p->out_act == MT_ACT_TANH || p->out_act == MT_ACT_IDENTITY, "mt_policy_grad.out_act must be MT_ACT_TANH or MT_ACT_IDENTITY");
+    MT_REQUIRE(h, p.width[l] >= 1 && p.width[l] <= MT_POLICY_MAX_WIDTH,
+               w + ".width[" + std::to_string(l) + "] must be 1.." + std::to_string(MT_POLICY_MAX_WIDTH));
+  MT_REQUIRE(h, L == 1 || p.hidden_act == MT_ACT_TANH || p.hidden_act == MT_ACT_RELU, w + ".hidden_act must be MT_ACT_TANH or MT_ACT_RELU");
+  MT_REQUIRE(h, p.out_act == MT_ACT_TANH || p.out_act == MT_ACT_IDENTITY, w + ".out_act must be MT_ACT_TANH or MT_ACT_IDENTITY");
   // (bit patterns: the build is -ffinite-math-only)
-  MT_REQUIRE(h, first_unusable(&p->out_scale, 1, kMaxFiniteBits) < 0, "mt_policy_grad.out_scale must be finite");
-  MT_REQUIRE(h, first_unusable(&p->scale, 1, kMaxFiniteBits) < 0, "mt_policy_grad.scale must be finite");
-  for (int j = 0; j < MT_MAX_DOF; ++j)  // (every handle has at least one joint; entries past D are not read)
-    MT_REQUIRE(h, first_unusable(&p->sigma[j], 1, kMaxFiniteBits) < 0 && (j == 0 ? p->sigma[j] > 0.f : p->sigma[j] >= 0.f),
-               "mt_policy_grad.sigma[" + std::to_string(j) + "] must be finite and > 0");
+  MT_REQUIRE(h, first_unusable(&p.out_scale, 1, kMaxFiniteBits) < 0, w + ".out_scale must be finite");
+  return MT_OK;
+}
+// ... sigma ahead of the handle: entries whose use depends on the handle's D may still be 0 (`n_known` of them are known
+// to be read: every handle has at least one joint)
+static int policy_sigma_screen(mt_handle h, const float* sigma, int n_known, const std::string& w) {
+  for (int j = 0; j < MT_MAX_DOF; ++j)
+    MT_REQUIRE(h, first_unusable(&sigma[j], 1, kMaxFiniteBits) < 0 && (j < n_known ? sigma[j] > 0.f : sigma[j] >= 0.f),
+               w + ".sigma[" + std::to_string(j) + "] must be finite and > 0");
+  return MT_OK;
+}
+// A buffer a call reads or writes, for the aliasing rules: `bytes` from `p` on (0: not given).
+struct Span {
+  const void* p;
+  size_t bytes;
+  const char* name;
+};
+static size_t rows_bytes(int64_t rows, int64_t ld, int64_t n, size_t elem = 4) { return (size_t)((rows - 1) * ld + n) * elem; }
+// Every output against the weights, against every input and against the outputs behind it.
+static int policy_overlap_screen(mt_handle h, const PolicyNet& p, const PolicyLayout& s, const Span* out, int n_out, const Span* in, int n_in,
+                                 const std::string& w) {
+  for (int a = 0; a < n_out; ++a) {
+    const std::string msg = w + "." + out[a].name + " overlaps ";
+    for (int l = 0; l < p.n_layers; ++l)
+      MT_REQUIRE(h, !bytes_overlap(out[a].p, out[a].bytes, p.weight[l], (size_t)s.n_out[l] * s.n_in[l] * 4) &&
+                        !bytes_overlap(out[a].p, out[a].bytes, p.bias[l], (size_t)s.n_out[l] * 4),
+                 msg + "weight / bias [" + std::to_string(l) + "]");
+    for (int b = 0; b < n_in; ++b) MT_REQUIRE(h, !bytes_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes), msg + in[b].name);
+    for (int b = a + 1; b < n_out; ++b) MT_REQUIRE(h, !bytes_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes), msg + out[b].name);
+  }
+  return MT_OK;
+}
+
+// mt_policy_grad and mt_value_grad behind their own struct_size checks: the value head's gradient is the policy's with one
+// output (n_last = 1), sigma = 1 (sigma NULL) and the target in the action's place (`act` names it in the messages).
+struct PolicyGradCall {
+  PolicyNet net;
+  const float* sigma;  // MT_MAX_DOF of them, or NULL: 1
+  int n_last;          // outputs of the last layer; 0 = the handle's D
+  const float* action;
+  int64_t act_ld;
+  const char* act;     // "action" / "target"
+  const char* act_ld_name;
+  const float* coef;
+  int64_t coef_ld;
+  float scale;
+  float* grad_out;
+  float* loss_out;
+  void* workspace;
+  size_t workspace_bytes;
+};
+static int policy_grad_call(mt_handle h, const PolicyGradCall& c, const std::string& w) {
+  const PolicyNet& p = c.net;
+  // what needs no handle: the scalars
+  int rc = policy_net_screen(h, p, w);
+  if (rc) return rc;
+  MT_REQUIRE(h, first_unusable(&c.scale, 1, kMaxFiniteBits) < 0, w + ".scale must be finite");
+  if (c.sigma && (rc = policy_sigma_screen(h, c.sigma, 1, w))) return rc;
   MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
-  for (int j = 0; j < h->D; ++j)
-    MT_REQUIRE(h, p->sigma[j] > 0.f, "mt_policy_grad.sigma[" + std::to_string(j) + "] must be finite and > 0");
+  const int L = p.n_layers;
+  const int D = c.n_last ? c.n_last : h->D;  // the outputs of the last layer
+  if (c.sigma)
+    for (int j = 0; j < D; ++j) MT_REQUIRE(h, c.sigma[j] > 0.f, w + ".sigma[" + std::to_string(j) + "] must be finite and > 0");
   PolicyLayout s;
-  MT_REQUIRE(h, policy_layout(h, L, p->width, p->flags, &s), "mt_policy_grad: not a policy shape");
-  const int T = p->n_steps;
+  MT_REQUIRE(h, policy_layout(h, L, p.width, p.flags, &s, c.n_last), w + ": not a policy shape");
+  const int T = p.n_steps;
   const int64_t n = h->n, P = s.P;
-  const int IN = s.n_in[0], D = h->D;
-  MT_REQUIRE(h, p->grad_out != nullptr, "mt_policy_grad.grad_out is NULL");
+  const int IN = s.n_in[0];
+  // policy_grad_kernel streams x as K triples and, with see_pose, r.D single words behind them: with r.D = h->D that is
+  // x as mt_rollout_policy lays it out; with another output count the same IN words are regrouped (the fmaf chain of an
+  // output runs over x in ascending order either way), which needs IN = 3 K' or 3 K' + r.D
+  const int x_singles = D == h->D ? ((p.flags & MT_POLICY_SEE_POSE) ? D : 0) : IN % 3;
+  if (x_singles != 0 && x_singles != D)
+    return fail(h, MT_ERR_UNSUPPORTED, w + ": MT_POLICY_SEE_POSE with " + std::to_string(h->D) + " joints (supported: 3, 4, 6, 7)");
+  MT_REQUIRE(h, c.grad_out != nullptr, w + ".grad_out is NULL");
   const size_t need = T ? (size_t)policy_grad_blocks(h, T) * (size_t)(P + 1) * sizeof(float) : 0;
   if (T) {
     for (int l = 0; l < L; ++l)
-      MT_REQUIRE(h, p->weight[l] != nullptr && p->bias[l] != nullptr, "mt_policy_grad.weight / bias [" + std::to_string(l) + "] is NULL");
-    MT_REQUIRE(h, p->obs != nullptr && p->action != nullptr && p->coef != nullptr, "mt_policy_grad.obs / action / coef is NULL");
-    MT_REQUIRE(h, p->obs_ld >= n, "mt_policy_grad.obs_ld is smaller than n_envs");
-    MT_REQUIRE(h, p->act_ld >= n, "mt_policy_grad.act_ld is smaller than n_envs");
-    MT_REQUIRE(h, p->coef_ld >= n, "mt_policy_grad.coef_ld is smaller than n_envs");
-    MT_REQUIRE(h, p->workspace != nullptr && ((uintptr_t)p->workspace & 3u) == 0, "mt_policy_grad.workspace is NULL or not 4-byte aligned");
-    MT_REQUIRE(h, p->workspace_bytes >= need,
-               "mt_policy_grad.workspace_bytes is smaller than mt_policy_grad_workspace() = " + std::to_string(need));
+      MT_REQUIRE(h, p.weight[l] != nullptr && p.bias[l] != nullptr, w + ".weight / bias [" + std::to_string(l) + "] is NULL");
+    MT_REQUIRE(h, p.obs != nullptr && c.action != nullptr && c.coef != nullptr, w + ".obs / " + c.act + " / coef is NULL");
+    MT_REQUIRE(h, p.obs_ld >= n, w + ".obs_ld is smaller than n_envs");
+    MT_REQUIRE(h, c.act_ld >= n, w + "." + c.act_ld_name + " is smaller than n_envs");
+    MT_REQUIRE(h, c.coef_ld >= n, w + ".coef_ld is smaller than n_envs");
+    MT_REQUIRE(h, c.workspace != nullptr && ((uintptr_t)c.workspace & 3u) == 0, w + ".workspace is NULL or not 4-byte aligned");
+    MT_REQUIRE(h, c.workspace_bytes >= need, w + ".workspace_bytes is smaller than " + w + "_workspace() = " + std::to_string(need));
     // the outputs against the inputs and against each other
-    const void* out[3] = {p->grad_out, p->loss_out, p->workspace};
-    const size_t out_bytes[3] = {(size_t)P * 4, p->loss_out ? (size_t)4 : 0, need};
-    const char* out_name[3] = {"grad_out", "loss_out", "workspace"};
-    for (int a = 0; a < 3; ++a) {
-      const std::string msg = std::string("mt_policy_grad.") + out_name[a] + " overlaps ";
-      for (int l = 0; l < L; ++l)
-        MT_REQUIRE(h, !bytes_overlap(out[a], out_bytes[a], p->weight[l], (size_t)s.n_out[l] * s.n_in[l] * 4) &&
-                          !bytes_overlap(out[a], out_bytes[a], p->bias[l], (size_t)s.n_out[l] * 4),
-                   msg + "weight / bias [" + std::to_string(l) + "]");
-      MT_REQUIRE(h, !bytes_overlap(out[a], out_bytes[a], p->obs, (size_t)(((int64_t)T * IN - 1) * p->obs_ld + n) * 4), msg + "obs");
-      MT_REQUIRE(h, !bytes_overlap(out[a], out_bytes[a], p->action, (size_t)(((int64_t)T * D - 1) * p->act_ld + n) * 4), msg + "action");
-      MT_REQUIRE(h, !bytes_overlap(out[a], out_bytes[a], p->coef, (size_t)(((int64_t)T - 1) * p->coef_ld + n) * 4), msg + "coef");
-      for (int b = a + 1; b < 3; ++b)
-        MT_REQUIRE(h, !bytes_overlap(out[a], out_bytes[a], out[b], out_bytes[b]), msg + out_name[b]);
-    }
+    const Span out[3] = {{c.grad_out, (size_t)P * 4, "grad_out"}, {c.loss_out, c.loss_out ? (size_t)4 : 0, "loss_out"}, {c.workspace, need, "workspace"}};
+    const Span in[3] = {{p.obs, rows_bytes((int64_t)T * IN, p.obs_ld, n), "obs"},
+                        {c.action, rows_bytes((int64_t)T * D, c.act_ld, n), c.act},
+                        {c.coef, rows_bytes(T, c.coef_ld, n), "coef"}};
+    if ((rc = policy_overlap_screen(h, p, s, out, 3, in, 3, w))) return rc;
   }
   MT_ENTER(h);
   PolicyGradArgs r{};
   for (int l = 0; l < L; ++l) {
-    r.w[l] = p->weight[l];
-    r.b[l] = p->bias[l];
+    r.w[l] = p.weight[l];
+    r.b[l] = p.bias[l];
     r.n_in[l] = s.n_in[l];
     r.n_out[l] = s.n_out[l];
     r.off[l] = s.off[l];
   }
   r.L = L;
   r.T = T;
-  r.K = h->K;
+  r.K = (IN - x_singles) / 3;
   r.D = D;
-  r.hidden_act = p->hidden_act;
-  r.out_act = p->out_act;
-  r.out_scale = p->out_scale;
-  for (int j = 0; j < D; ++j) r.inv_var[j] = (float)(1.0 / ((double)p->sigma[j] * (double)p->sigma[j]));
-  r.see_pose = (p->flags & MT_POLICY_SEE_POSE) ? 1u : 0u;
-  r.obs = p->obs;
-  r.obs_ld = p->obs_ld;
-  r.action = p->action;
-  r.act_ld = p->act_ld;
-  r.coef = p->coef;
-  r.coef_ld = p->coef_ld;
+  r.hidden_act = p.hidden_act;
+  r.out_act = p.out_act;
+  r.out_scale = p.out_scale;
+  for (int j = 0; j < D; ++j) r.inv_var[j] = c.sigma ? (float)(1.0 / ((double)c.sigma[j] * (double)c.sigma[j])) : 1.f;
+  r.see_pose = x_singles ? 1u : 0u;
+  r.obs = p.obs;
+  r.obs_ld = p.obs_ld;
+  r.action = c.action;
+  r.act_ld = c.act_ld;
+  r.coef = c.coef;
+  r.coef_ld = c.coef_ld;
   r.n = n;
   r.tiles_per_step = (n + kBlock - 1) / kBlock;
   r.tiles = (int64_t)T * r.tiles_per_step;
   r.P = P;
-  r.partials = static_cast<float*>(p->workspace);
+  r.partials = static_cast<float*>(c.workspace);
   r.blocks = T ? (int32_t)policy_grad_blocks(h, T) : 0;
-  r.scale = p->scale;
-  r.grad = p->grad_out;
-  r.loss = p->loss_out;
+  r.scale = c.scale;
+  r.grad = c.grad_out;
+  r.loss = c.loss_out;
   if (T) {
     // the smallest compiled (extent, chunks of x) that holds the policy: kernels.h PolicyGradShape
     if (s.widest <= 32)
@@ -2671,11 +2742,151 @@ int mt_policy_grad(mt_handle h, const struct mt_policy_grad* p) {
       hipLaunchKernelGGL((policy_grad_kernel<64, 1>), dim3((unsigned)r.blocks), dim3(kBlock), 0, h->stream, r);
     else
       hipLaunchKernelGGL((policy_grad_kernel<64, 2>), dim3((unsigned)r.blocks), dim3(kBlock), 0, h->stream, r);
-    int rc = check_launch(h, "policy_grad_kernel");
-    if (rc) return rc;
+    if ((rc = check_launch(h, "policy_grad_kernel"))) return rc;
   }
   hipLaunchKernelGGL(policy_grad_reduce_kernel, grid_for(P + 1), dim3(kBlock), 0, h->stream, r);
   return check_launch(h, "policy_grad_reduce_kernel");
+}
+
+int mt_policy_grad(mt_handle h, const struct mt_policy_grad* p) {
+  MT_REQUIRE(h, p != nullptr, "policy_grad is NULL");  // (the struct first: its size is checked with or without a handle)
+  MT_REQUIRE(h, p->struct_size == (int32_t)sizeof(struct mt_policy_grad), "mt_policy_grad.struct_size does not match this library");
+  const PolicyGradCall c{MT_POLICY_NET(p), p->sigma, 0, p->action, p->act_ld, "action", "act_ld", p->coef, p->coef_ld, p->scale,
+                         p->grad_out, p->loss_out, p->workspace, p->workspace_bytes};
+  return policy_grad_call(h, c, "mt_policy_grad");
+}
+
+size_t mt_value_grad_workspace(mt_handle h, int n_layers, const int32_t width[2], uint32_t flags, int n_steps) {
+  return policy_grad_workspace(h, n_layers, width, flags, n_steps, 1);
+}
+int mt_value_grad(mt_handle h, const struct mt_value_grad* p) {
+  MT_REQUIRE(h, p != nullptr, "value_grad is NULL");  // (the struct first: its size is checked with or without a handle)
+  MT_REQUIRE(h, p->struct_size == (int32_t)sizeof(struct mt_value_grad), "mt_value_grad.struct_size does not match this library");
+  const PolicyGradCall c{MT_POLICY_NET(p), nullptr, 1, p->target, p->target_ld, "target", "target_ld", p->coef, p->coef_ld, p->scale,
+                         p->grad_out, p->loss_out, p->workspace, p->workspace_bytes};
+  return policy_grad_call(h, c, "mt_value_grad");
+}
+
+int mt_policy_eval(mt_handle h, const struct mt_policy_eval* p) {
+  MT_REQUIRE(h, p != nullptr, "policy_eval is NULL");  // (the struct first: its size is checked with or without a handle)
+  MT_REQUIRE(h, p->struct_size == (int32_t)sizeof(struct mt_policy_eval), "mt_policy_eval.struct_size does not match this library");
+  const std::string w = "mt_policy_eval";
+  const PolicyNet net = MT_POLICY_NET(p);
+  int rc = policy_net_screen(h, net, w);
+  if (rc) return rc;
+  MT_REQUIRE(h, p->n_out >= 0 && p->n_out <= MT_MAX_DOF, w + ".n_out must be 0 (the handle's D) or 1.." + std::to_string(MT_MAX_DOF));
+  MT_REQUIRE(h, p->mean_out != nullptr || p->logp_out != nullptr, w + ": mean_out and logp_out are both NULL");
+  MT_REQUIRE(h, p->logp_out == nullptr || p->action != nullptr, w + ".logp_out needs action");
+  if (p->logp_out && (rc = policy_sigma_screen(h, p->sigma, p->n_out ? p->n_out : 1, w))) return rc;
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  const int L = p->n_layers, T = p->n_steps, NO = p->n_out ? p->n_out : h->D;
+  if (p->logp_out)
+    for (int j = 0; j < NO; ++j) MT_REQUIRE(h, p->sigma[j] > 0.f, w + ".sigma[" + std::to_string(j) + "] must be finite and > 0");
+  PolicyLayout s;
+  MT_REQUIRE(h, policy_layout(h, L, p->width, p->flags, &s, NO), w + ": not a policy shape");
+  if (T == 0) return MT_OK;
+  const int64_t n = h->n;
+  const int IN = s.n_in[0];
+  for (int l = 0; l < L; ++l)
+    MT_REQUIRE(h, p->weight[l] != nullptr && p->bias[l] != nullptr, w + ".weight / bias [" + std::to_string(l) + "] is NULL");
+  MT_REQUIRE(h, p->obs != nullptr, w + ".obs is NULL");
+  MT_REQUIRE(h, p->obs_ld >= n, w + ".obs_ld is smaller than n_envs");
+  MT_REQUIRE(h, p->mean_out == nullptr || p->mean_ld >= n, w + ".mean_ld is smaller than n_envs");
+  MT_REQUIRE(h, p->logp_out == nullptr || p->act_ld >= n, w + ".act_ld is smaller than n_envs");
+  MT_REQUIRE(h, p->logp_out == nullptr || p->logp_ld >= n, w + ".logp_ld is smaller than n_envs");
+  const bool lp = p->logp_out != nullptr;  // (without it the actions are not read)
+  const Span out[2] = {{p->mean_out, p->mean_out ? rows_bytes((int64_t)T * NO, p->mean_ld, n) : 0, "mean_out"},
+                       {p->logp_out, lp ? rows_bytes(T, p->logp_ld, n) : 0, "logp_out"}};
+  const Span in[2] = {{p->obs, rows_bytes((int64_t)T * IN, p->obs_ld, n), "obs"},
+                      {p->action, lp ? rows_bytes((int64_t)T * NO, p->act_ld, n) : 0, "action"}};
+  if ((rc = policy_overlap_screen(h, net, s, out, 2, in, 2, w))) return rc;
+  MT_ENTER(h);
+  PolicyEvalArgs r{};
+  for (int l = 0; l < L; ++l) {
+    r.w[l] = p->weight[l];
+    r.b[l] = p->bias[l];
+    r.n_in[l] = s.n_in[l];
+    r.n_out[l] = s.n_out[l];
+  }
+  r.L = L;
+  r.K = h->K;
+  r.n_pose = IN - 3 * h->K;
+  r.NO = NO;
+  r.hidden_act = p->hidden_act;
+  r.out_act = p->out_act;
+  r.out_scale = p->out_scale;
+  if (lp)
+    for (int j = 0; j < NO; ++j) r.inv_var[j] = (float)(1.0 / ((double)p->sigma[j] * (double)p->sigma[j]));
+  r.obs = p->obs;
+  r.obs_ld = p->obs_ld;
+  r.action = lp ? p->action : nullptr;
+  r.act_ld = p->act_ld;
+  r.mean = p->mean_out;
+  r.mean_ld = p->mean_ld;
+  r.logp = p->logp_out;
+  r.logp_ld = p->logp_ld;
+  r.n = n;
+  // a block per tile of kBlock envs (x) of one step (y); the extent as mt_policy_grad picks it
+  const dim3 grid((unsigned)((n + kBlock - 1) / kBlock), (unsigned)T);
+  if (s.widest <= 32)
+    hipLaunchKernelGGL((policy_eval_kernel<32>), grid, dim3(kBlock), 0, h->stream, r);
+  else
+    hipLaunchKernelGGL((policy_eval_kernel<64>), grid, dim3(kBlock), 0, h->stream, r);
+  return check_launch(h, "policy_eval_kernel");
+}
+
+int mt_gae(mt_handle h, const struct mt_gae* s) {
+  MT_REQUIRE(h, s != nullptr, "gae is NULL");  // (the struct first: its size is checked with or without a handle)
+  MT_REQUIRE(h, s->struct_size == (int32_t)sizeof(struct mt_gae), "mt_gae.struct_size does not match this library");
+  MT_REQUIRE(h, s->reserved == 0, "mt_gae.reserved must be 0");
+  MT_REQUIRE(h, (s->flags & ~(uint32_t)MT_GAE_MASK_AFTER_DONE) == 0, "mt_gae.flags: unknown MT_GAE_* flag");
+  MT_REQUIRE(h, s->n_steps >= 0 && s->n_steps <= 65535, "mt_gae.n_steps must be 0..65535");
+  // (bit patterns: the build is -ffinite-math-only)
+  MT_REQUIRE(h, first_unusable(&s->gamma, 1, kMaxFiniteBits) < 0 && s->gamma >= 0.f && s->gamma <= 1.f, "mt_gae.gamma must be in [0, 1]");
+  MT_REQUIRE(h, first_unusable(&s->lambda, 1, kMaxFiniteBits) < 0 && s->lambda >= 0.f && s->lambda <= 1.f, "mt_gae.lambda must be in [0, 1]");
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  if (s->n_steps == 0) return MT_OK;
+  const int64_t n = h->n, T = s->n_steps;
+  MT_REQUIRE(h, s->reward_log != nullptr && s->done_log != nullptr && s->value != nullptr, "mt_gae.reward_log / done_log / value is NULL");
+  MT_REQUIRE(h, s->adv_out != nullptr, "mt_gae.adv_out is NULL");
+  MT_REQUIRE(h, s->log_ld >= n, "mt_gae.log_ld is smaller than n_envs");
+  MT_REQUIRE(h, s->value_ld >= n, "mt_gae.value_ld is smaller than n_envs");
+  MT_REQUIRE(h, s->adv_ld >= n, "mt_gae.adv_ld is smaller than n_envs");
+  MT_REQUIRE(h, s->ret_out == nullptr || s->ret_ld >= n, "mt_gae.ret_ld is smaller than n_envs");
+  MT_REQUIRE(h, s->weight_out == nullptr || s->weight_ld >= n, "mt_gae.weight_ld is smaller than n_envs");
+  const Span out[3] = {{s->adv_out, rows_bytes(T, s->adv_ld, n), "adv_out"},
+                       {s->ret_out, s->ret_out ? rows_bytes(T, s->ret_ld, n) : 0, "ret_out"},
+                       {s->weight_out, s->weight_out ? rows_bytes(T, s->weight_ld, n) : 0, "weight_out"}};
+  const Span in[4] = {{s->reward_log, rows_bytes(T, s->log_ld, n, 1), "reward_log"},
+                      {s->done_log, rows_bytes(T, s->log_ld, n, 1), "done_log"},
+                      {s->value, rows_bytes(T, s->value_ld, n), "value"},
+                      {s->last_value, s->last_value ? (size_t)n * 4 : 0, "last_value"}};
+  for (int a = 0; a < 3; ++a) {
+    const std::string msg = std::string("mt_gae.") + out[a].name + " overlaps ";
+    for (int b = 0; b < 4; ++b) MT_REQUIRE(h, !bytes_overlap(out[a].p, out[a].bytes, in[b].p, in[b].bytes), msg + in[b].name);
+    for (int b = a + 1; b < 3; ++b) MT_REQUIRE(h, !bytes_overlap(out[a].p, out[a].bytes, out[b].p, out[b].bytes), msg + out[b].name);
+  }
+  MT_ENTER(h);
+  GaeArgs r{};
+  r.reward = s->reward_log;
+  r.done = s->done_log;
+  r.log_ld = s->log_ld;
+  r.value = s->value;
+  r.value_ld = s->value_ld;
+  r.last_value = s->last_value;
+  r.gamma = s->gamma;
+  r.gl = s->gamma * s->lambda;  // one fp32 product (-ffp-contract=off)
+  r.adv = s->adv_out;
+  r.adv_ld = s->adv_ld;
+  r.ret = s->ret_out;
+  r.ret_ld = s->ret_ld;
+  r.weight = s->weight_out;
+  r.weight_ld = s->weight_ld;
+  r.n = n;
+  r.T = s->n_steps;
+  r.mask_after_done = (s->flags & MT_GAE_MASK_AFTER_DONE) ? 1u : 0u;
+  hipLaunchKernelGGL(gae_kernel, grid_for(n), dim3(kBlock), 0, h->stream, r);
+  return check_launch(h, "gae_kernel");
 }
 
 int mt_reward_to_go(mt_handle h, const struct mt_reward_to_go* s) {

@@ -3342,6 +3342,146 @@ __global__ __launch_bounds__(kBlock) void reward_to_go_kernel(const RewardToGoAr
 }
 
 // ---------------------------------------------------------------------------
+// The forward pass alone over logged observations (mt_policy_eval) and the advantages a critic's values turn the logs into
+// (mt_gae).  As above, neither depends on the DH table nor touches a handle's state.
+//
+// policy_eval_kernel<W>: one sample (t, i) per lane, block (x, y) = tile x of kBlock consecutive envs of step y.  No LDS,
+// no barrier: a lane behind n_envs returns at once.  The forward pass is policy_grad_kernel's text -- policy_bias /
+// policy_feed over x streamed from obs in triples, policy_finish, policy_hidden, policy_dot -- so mu has the bits of the
+// rollout and of the gradient; the weights are wave-uniform scalar operands, h0 / h1 register arrays that policy_hidden
+// rotates (no register array is indexed dynamically), and only about 2 W floats are live: no backward pass keeps them.
+// logp follows policy_grad_kernel's sequence word for word (e, d = e * inv_var, lp = fmaf(e, d, lp), -0.5f * lp).
+// ---------------------------------------------------------------------------
+struct PolicyEvalArgs {
+  const float* w[3];
+  const float* b[3];
+  int32_t n_in[3], n_out[3];  // per layer, as PolicyArgs; n_out[L - 1] = NO
+  int32_t L, K, n_pose, NO;   // n_pose: the joint angles behind the 3 K words of x (0 without MT_POLICY_SEE_POSE)
+  int32_t hidden_act, out_act;
+  float out_scale;
+  float inv_var[MT_MAX_DOF];  // the fp32 nearest to 1 / sigma_j^2 (read with logp)
+  const float* obs;  // [T * IN][obs_ld]
+  int64_t obs_ld;
+  const float* action;  // [T * NO][act_ld] or NULL
+  int64_t act_ld;
+  float* mean;  // [T * NO][mean_ld] or NULL
+  int64_t mean_ld;
+  float* logp;  // [T][logp_ld] or NULL (then action is not read)
+  int64_t logp_ld;
+  int64_t n;  // envs
+};
+
+template <int W>
+__global__ __launch_bounds__(kBlock) void policy_eval_kernel(const PolicyEvalArgs r) {
+  const int64_t t = blockIdx.y;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= r.n) return;
+  const int L = r.L, IN = r.n_in[0], NO = r.NO;
+  const weight_ptr w0 = as_weights(r.w[0]), b0 = as_weights(r.b[0]);
+  const weight_ptr wl = as_weights(r.w[L - 1]), bl = as_weights(r.b[L - 1]);  // the output layer
+  const float* xcol = r.obs + t * IN * r.obs_ld + i;                          // x_k = xcol[k obs_ld]
+  auto first_layer = [&](auto& acc, int n_out) {
+    policy_bias(acc, b0, n_out);
+    for (int k = 0; k < r.K; ++k) {
+      float tri[3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) tri[q] = xcol[(int64_t)(3 * k + q) * r.obs_ld];
+      policy_feed(acc, w0, IN, n_out, 3 * k, tri);
+    }
+    for (int j = 0; j < r.n_pose; ++j) {
+      const float xj[1] = {xcol[(int64_t)(3 * r.K + j) * r.obs_ld]};
+      policy_feed(acc, w0, IN, n_out, 3 * r.K + j, xj);
+    }
+  };
+
+  float y[MT_MAX_DOF];
+  if (L == 1) {
+    first_layer(y, NO);
+  } else {
+    float h0[W];
+    first_layer(h0, r.n_out[0]);
+    policy_finish(h0, r.hidden_act, r.n_out[0]);
+    if (L == 2) {
+#pragma unroll
+      for (int j = 0; j < MT_MAX_DOF; ++j) y[j] = j < NO ? policy_dot<W>(wl + (int64_t)j * r.n_in[1], bl[j], r.n_in[1], h0) : 0.f;
+    } else {
+      float h1[W];
+#pragma unroll
+      for (int o = 0; o < W; ++o) h1[o] = 0.f;
+      policy_hidden<W>(as_weights(r.w[1]), as_weights(r.b[1]), r.n_in[1], r.n_out[1], r.hidden_act, h0, h1);
+#pragma unroll
+      for (int j = 0; j < MT_MAX_DOF; ++j) y[j] = j < NO ? policy_dot<W>(wl + (int64_t)j * r.n_in[2], bl[j], r.n_in[2], h1) : 0.f;
+    }
+  }
+
+  float lp = 0.f;
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < MT_MAX_DOF; ++j) {
+    if (j < NO) {
+      const float tj = policy_act(r.out_act, y[j]);
+      const float mu = r.out_scale * tj;
+      if (r.mean) r.mean[(t * NO + j) * r.mean_ld + i] = mu;
+      if (r.logp) {
+        const float a = r.action[(t * NO + j) * r.act_ld + i];
+        bad |= unusable_angle(a);
+        const float e = a - mu;
+        const float d = e * r.inv_var[j];
+        lp = __builtin_fmaf(e, d, lp);
+      }
+    }
+  }
+  if (r.logp) r.logp[t * r.logp_ld + i] = bad ? 0.f : -0.5f * lp;
+}
+
+struct GaeArgs {
+  const int8_t* reward;  // [T][log_ld]
+  const uint8_t* done;
+  int64_t log_ld;
+  const float* value;  // [T][value_ld]
+  int64_t value_ld;
+  const float* last_value;  // [n] or NULL
+  float gamma, gl;          // gl: the fp32 product gamma * lambda
+  float* adv;               // [T][adv_ld]
+  int64_t adv_ld;
+  float* ret;  // [T][ret_ld] or NULL
+  int64_t ret_ld;
+  float* weight;  // [T][weight_ld] or NULL
+  int64_t weight_ld;
+  int64_t n;
+  int32_t T;
+  uint32_t mask_after_done;
+};
+// one lane per env, backwards over t, as reward_to_go_kernel: delta = fmaf(gamma, done_t ? 0 : V_t+1, r_t) - V_t,
+// A_t = fmaf(gl, done_t ? 0 : A_t+1, delta), ret_t = A_t + V_t; steps behind the first done are 0 (and not read) when masked
+__global__ __launch_bounds__(kBlock) void gae_kernel(const GaeArgs r) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= r.n) return;
+  int first = r.T;
+  if (r.mask_after_done) {
+    for (int t = r.T - 1; t >= 0; --t)
+      if (r.done[(int64_t)t * r.log_ld + i]) first = t;
+  }
+  float A = 0.f, Vn = r.last_value ? r.last_value[i] : 0.f;
+  for (int t = r.T - 1; t >= 0; --t) {
+    float adv = 0.f, ret = 0.f, wt = 0.f;
+    if (t <= first) {
+      const bool d = r.done[(int64_t)t * r.log_ld + i] != 0;
+      const float V = r.value[(int64_t)t * r.value_ld + i];
+      const float delta = __builtin_fmaf(r.gamma, d ? 0.f : Vn, (float)r.reward[(int64_t)t * r.log_ld + i]) - V;
+      A = __builtin_fmaf(r.gl, d ? 0.f : A, delta);
+      adv = A;
+      ret = A + V;
+      wt = 1.f;
+      Vn = V;
+    }
+    r.adv[(int64_t)t * r.adv_ld + i] = adv;
+    if (r.ret) r.ret[(int64_t)t * r.ret_ld + i] = ret;
+    if (r.weight) r.weight[(int64_t)t * r.weight_ld + i] = wt;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // mt_shoot's evaluation: C candidate tapes per env scored from the SAME resident state, the best one named.  For env i
 // and candidate c, returns[c][i] is what rollout_tape_kernel's dry run writes to return_out[i] for plane c, bit for bit;
 // best[i] is the smallest c whose return is maximal.  Nothing resident is written.

@@ -619,20 +619,26 @@ class StepEngine:
         return res or None
 
     # ---- evolution strategies: a population of policies, one row of flat parameters per member ----------------------------
-    def _policy_shapes(self, widths, see_pose=False):
-        """[(out, in), ...] of the linear layers of a policy with hidden `widths` on this engine."""
+    def _policy_shapes(self, widths, see_pose=False, n_out=None):
+        """[(out, in), ...] of the linear layers of a policy with hidden `widths` on this engine; the last one has `n_out`
+        outputs (None: D, a policy; a value head has 1)."""
         widths = tuple(int(w) for w in widths)
         if len(widths) > L.POLICY_MAX_LAYERS - 1 or any(not 1 <= w <= L.POLICY_MAX_WIDTH for w in widths):
             raise ValueError(f"widths must be at most {L.POLICY_MAX_LAYERS - 1} hidden widths of 1..{L.POLICY_MAX_WIDTH}, got {widths}")
         fan_in, shapes = 3 * self.obj_number + (self.dof if see_pose else 0), []
-        for fan_out in widths + (self.dof,):
+        for fan_out in widths + (self.dof if n_out is None else int(n_out),):
             shapes.append((fan_out, fan_in))
             fan_in = fan_out
         return shapes
 
-    def policy_size(self, widths=(), see_pose=False) -> int:
-        """P, the number of floats of a policy with hidden `widths`: sum of out * in + out over its layers."""
-        return sum(o * i + o for o, i in self._policy_shapes(widths, see_pose))
+    def policy_size(self, widths=(), see_pose=False, n_out=None) -> int:
+        """P, the number of floats of a policy with hidden `widths`: sum of out * in + out over its layers (`n_out`: the
+        outputs of the last one, None = D)."""
+        return sum(o * i + o for o, i in self._policy_shapes(widths, see_pose, n_out))
+
+    def value_size(self, widths=(), see_pose=False) -> int:
+        """P_v, the number of floats of a value head with hidden `widths`: a policy whose last layer has one output."""
+        return self.policy_size(widths, see_pose, 1)
 
     @staticmethod
     def flatten_policy(layers):
@@ -644,9 +650,9 @@ class StepEngine:
             pairs = [tuple(p) for p in layers]
         return torch.cat([t.detach().reshape(-1) for pair in pairs for t in pair]).to(torch.float32).contiguous()
 
-    def unflatten_policy(self, theta, widths=(), see_pose=False):
+    def unflatten_policy(self, theta, widths=(), see_pose=False, n_out=None):
         """[(weight, bias), ...] VIEWS of `theta` (P floats, a row of a population included): what rollout_policy accepts."""
-        shapes = self._policy_shapes(widths, see_pose)
+        shapes = self._policy_shapes(widths, see_pose, n_out)
         need = sum(o * i + o for o, i in shapes)
         if theta.dim() != 1 or theta.shape[0] < need or theta.stride(0) != 1:
             raise ValueError(f"theta must be a dense vector of at least P = {need} floats, got shape {tuple(theta.shape)}")
@@ -655,6 +661,10 @@ class StepEngine:
             out.append((theta[off:off + o * i].view(o, i), theta[off + o * i:off + o * i + o]))
             off += o * i + o
         return out
+
+    def unflatten_value(self, theta, widths=(), see_pose=False):
+        """[(weight, bias), ...] VIEWS of a value head's flat `theta` (P_v floats): what values / value_grad accept."""
+        return self.unflatten_policy(theta, widths, see_pose, 1)
 
     def _members(self, members):
         m = int(members)
@@ -851,6 +861,44 @@ class StepEngine:
             raise ValueError(f"{name}: envs must be contiguous and the rows a constant ld >= N apart, got strides {tuple(st)}")
         return T, ld
 
+    def _policy_net_arg(self, arg, layers_or_theta, widths, hidden, out, see_pose, n_out):
+        """The network of policy_grad / policy_eval / value_grad into `arg` (weight, bias, width): `layers_or_theta` is a list
+        of (weight, bias), a torch.nn.Sequential, or the flat theta of flatten_policy with the hidden `widths`; the last layer
+        has `n_out` outputs.  -> (tensors to keep alive, number of layers, IN, P)."""
+        import torch
+        for name, v, allowed in (("hidden", hidden, ("tanh", "relu")), ("out", out, ("tanh", "identity"))):
+            if v not in allowed:
+                raise ValueError(f"{name} must be one of {allowed}, got {v!r}")
+        dev = torch.device("cuda", self.device)
+        d = self.dof
+        if _is_torch_tensor(layers_or_theta):
+            p = self.policy_size(widths, see_pose, n_out)
+            pairs = self.unflatten_policy(self._flat_vector(layers_or_theta, "theta", p), widths, see_pose, n_out)
+        else:
+            pairs = self._policy_layers(layers_or_theta, hidden, out)
+        if not 1 <= len(pairs) <= L.POLICY_MAX_LAYERS:
+            raise ValueError(f"a policy has 1..{L.POLICY_MAX_LAYERS} linear layers, got {len(pairs)}")
+        n_in = 3 * self.obj_number + (d if see_pose else 0)
+        keep, fan_in, p = [], n_in, 0
+        for l, (w, b) in enumerate(pairs):
+            w, b = w.detach(), b.detach()
+            fan_out = n_out if l == len(pairs) - 1 else int(w.shape[0]) if w.dim() == 2 else -1
+            if tuple(w.shape) != (fan_out, fan_in) or tuple(b.shape) != (fan_out,):
+                raise ValueError(f"layer {l}: weight must be ({fan_out if fan_out > 0 else 'out'}, {fan_in}) and bias (out,), got "
+                                 f"{tuple(w.shape)} and {tuple(b.shape)}")
+            if l < len(pairs) - 1 and not 1 <= fan_out <= L.POLICY_MAX_WIDTH:
+                raise ValueError(f"layer {l}: width must be 1..{L.POLICY_MAX_WIDTH}, got {fan_out}")
+            for what, t in (("weight", w), ("bias", b)):
+                if t.dtype != torch.float32 or not t.is_cuda or t.device != dev or not t.is_contiguous():
+                    raise ValueError(f"layer {l}: {what} must be a contiguous float32 tensor on {dev}")
+            keep += [w, b]
+            arg.weight[l], arg.bias[l] = w.data_ptr(), b.data_ptr()
+            if l < len(pairs) - 1:
+                arg.width[l] = fan_out
+            p += fan_out * fan_in + fan_out
+            fan_in = fan_out
+        return keep, len(pairs), n_in, p
+
     def reward_to_go(self, reward_log, done_log, gamma=1.0, baseline=0.0, mask_after_done=False, out=None):
         """The discounted reward-to-go of rollout_policy's logs (mt_reward_to_go): R_t = r_t + gamma * (0 if done_t else
         R_t+1), minus `baseline`, as a (T, N) float32 device tensor -- policy_grad's usual `coef`.  mask_after_done=True
@@ -896,38 +944,10 @@ class StepEngine:
         the same bits.  Two launches, no host wait; the workspace is cached on the engine.  Stream behaviour as
         rollout_actions; nothing resident is read or written."""
         import torch
-        for name, v, allowed in (("hidden", hidden, ("tanh", "relu")), ("out", out, ("tanh", "identity"))):
-            if v not in allowed:
-                raise ValueError(f"{name} must be one of {allowed}, got {v!r}")
         dev = torch.device("cuda", self.device)
         d = self.dof
-        if _is_torch_tensor(layers_or_theta):
-            p = self.policy_size(widths, see_pose)
-            pairs = self.unflatten_policy(self._flat_vector(layers_or_theta, "theta", p), widths, see_pose)
-        else:
-            pairs = self._policy_layers(layers_or_theta, hidden, out)
-        if not 1 <= len(pairs) <= L.POLICY_MAX_LAYERS:
-            raise ValueError(f"a policy has 1..{L.POLICY_MAX_LAYERS} linear layers, got {len(pairs)}")
-        n_in = 3 * self.obj_number + (d if see_pose else 0)
         arg = L.MtPolicyGrad()
-        keep, fan_in, p = [], n_in, 0
-        for l, (w, b) in enumerate(pairs):
-            w, b = w.detach(), b.detach()
-            fan_out = d if l == len(pairs) - 1 else int(w.shape[0]) if w.dim() == 2 else -1
-            if tuple(w.shape) != (fan_out, fan_in) or tuple(b.shape) != (fan_out,):
-                raise ValueError(f"layer {l}: weight must be ({fan_out if fan_out > 0 else 'out'}, {fan_in}) and bias (out,), got "
-                                 f"{tuple(w.shape)} and {tuple(b.shape)}")
-            if l < len(pairs) - 1 and not 1 <= fan_out <= L.POLICY_MAX_WIDTH:
-                raise ValueError(f"layer {l}: width must be 1..{L.POLICY_MAX_WIDTH}, got {fan_out}")
-            for what, t in (("weight", w), ("bias", b)):
-                if t.dtype != torch.float32 or not t.is_cuda or t.device != dev or not t.is_contiguous():
-                    raise ValueError(f"layer {l}: {what} must be a contiguous float32 tensor on {dev}")
-            keep += [w, b]
-            arg.weight[l], arg.bias[l] = w.data_ptr(), b.data_ptr()
-            if l < len(pairs) - 1:
-                arg.width[l] = fan_out
-            p += fan_out * fan_in + fan_out
-            fan_in = fan_out
+        keep, n_layers, n_in, p = self._policy_net_arg(arg, layers_or_theta, widths, hidden, out, see_pose, d)
         sig = np.ones(L.MT_MAX_DOF, dtype=np.float32)
         sig[:d] = np.broadcast_to(np.asarray(sigma, dtype=np.float32), (d,))
         if not (np.isfinite(sig).all() and (sig > 0).all()):
@@ -945,7 +965,7 @@ class StepEngine:
             self._flat_vector(grad_out, "grad_out", p)
         loss_t = torch.zeros(1, dtype=torch.float32, device=dev) if loss else None
         arg.struct_size = C.sizeof(L.MtPolicyGrad)
-        arg.n_steps, arg.n_layers = T, len(pairs)
+        arg.n_steps, arg.n_layers = T, n_layers
         arg.hidden_act, arg.out_act = self._ACTIVATIONS[hidden], self._ACTIVATIONS[out]
         arg.out_scale, arg.scale = float(out_scale), float(scale)
         arg.sigma[:] = sig.tolist()
@@ -954,7 +974,7 @@ class StepEngine:
         arg.obs_ld, arg.act_ld, arg.coef_ld = obs_ld, act_ld, coef_ld
         arg.grad_out = grad_out.data_ptr()
         arg.loss_out = loss_t.data_ptr() if loss else None
-        need = int(self._lib.mt_policy_grad_workspace(self._h, len(pairs), arg.width, arg.flags, T))
+        need = int(self._lib.mt_policy_grad_workspace(self._h, n_layers, arg.width, arg.flags, T))
         ws = getattr(self, "_pg_workspace", None)
         if need and (ws is None or ws.numel() * 4 < need):
             ws = self._pg_workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
@@ -962,6 +982,158 @@ class StepEngine:
         arg.workspace_bytes = ws.numel() * 4 if need else 0
         arg.reserved = 0
         self._torch_call(self._lib.mt_policy_grad, C.byref(arg), commits=False)
+        del keep
+        return (grad_out, loss_t) if loss else grad_out
+
+    # ---- a critic and GAE weights: the forward pass over the logs, the advantages, the value head's gradient ---------------
+    def policy_eval(self, layers_or_theta, obs, *, actions=None, sigma=None, n_out=None, widths=(), hidden="tanh", out="tanh",
+                    out_scale=180.0, see_pose=False, mean=True, logp=None):
+        """The MLP's forward pass over logged observations (mt_policy_eval): `mean` (T, n_out, N), mu = out_scale *
+        out(y_L) for every sample, bit for bit what rollout_policy and policy_grad compute for that x, and -- with `actions`
+        (T, n_out, N) and `sigma` (a float or n_out floats, > 0) -- `logp` (T, N), -1/2 sum_j ((a_j - mu_j) / sigma_j)^2 in
+        policy_grad's own fp32 sequence; a sample with an unusable action gets logp exactly 0.  n_out: the outputs of the
+        last layer (None = D, a policy; a value head has 1).  logp=None means "when actions are given"; mean=False skips
+        the mean; either may be a tensor to write into (a [..., :N] view of a wider buffer included).  The network, obs and the views accepted are policy_grad's.  Returns a dict of float32 device tensors.
+        One launch, no host wait; stream behaviour as rollout_actions; nothing resident is read or written."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        no = self.dof if n_out is None else int(n_out)
+        if not 1 <= no <= L.MT_MAX_DOF:
+            raise ValueError(f"n_out must be 1..{L.MT_MAX_DOF}, got {n_out!r}")
+        mean_given, logp_given = _is_torch_tensor(mean), _is_torch_tensor(logp)
+        logp = actions is not None if logp is None else logp
+        if (logp_given or logp) and (actions is None or sigma is None):
+            raise ValueError("logp needs actions and sigma")
+        if not (mean_given or mean or logp_given or logp):
+            raise ValueError("nothing to compute: mean=False and no logp")
+        arg = L.MtPolicyEval()
+        keep, n_layers, n_in, _ = self._policy_net_arg(arg, layers_or_theta, widths, hidden, out, see_pose, no)
+        if not np.isfinite(np.float32(out_scale)):
+            raise ValueError("out_scale must be finite")
+        T, obs_ld = self._log_rows(obs, "obs", n_in, torch.float32)
+        res = {}
+        arg.struct_size = C.sizeof(L.MtPolicyEval)
+        arg.n_steps, arg.n_layers, arg.n_out = T, n_layers, no
+        arg.hidden_act, arg.out_act = self._ACTIVATIONS[hidden], self._ACTIVATIONS[out]
+        arg.out_scale = float(out_scale)
+        arg.flags = L.POLICY_SEE_POSE if see_pose else 0
+        arg.obs, arg.obs_ld = (obs.data_ptr() if T else None), obs_ld
+        if mean_given or mean:
+            res["mean"] = mean if mean_given else torch.empty((T, no, self.n_envs), dtype=torch.float32, device=dev)
+            Tm, arg.mean_ld = self._log_rows(res["mean"], "mean", no, torch.float32)
+            if Tm != T:
+                raise ValueError(f"mean must have T = {T} steps")
+            arg.mean_out = res["mean"].data_ptr()
+        if logp_given or logp:
+            sig = np.ones(L.MT_MAX_DOF, dtype=np.float32)
+            sig[:no] = np.broadcast_to(np.asarray(sigma, dtype=np.float32), (no,))
+            if not (np.isfinite(sig).all() and (sig > 0).all()):
+                raise ValueError(f"sigma must be finite and > 0, got {sigma!r}")
+            Ta, act_ld = self._log_rows(actions, "actions", no, torch.float32)
+            if Ta != T:
+                raise ValueError(f"obs and actions must have the same number of steps, got {T}, {Ta}")
+            arg.sigma[:] = sig.tolist()
+            arg.action, arg.act_ld = (actions.data_ptr() if T else None), act_ld
+            res["logp"] = logp if logp_given else torch.empty((T, self.n_envs), dtype=torch.float32, device=dev)
+            Tl, arg.logp_ld = self._log_rows(res["logp"], "logp", None, torch.float32)
+            if Tl != T:
+                raise ValueError(f"logp must have T = {T} rows")
+            arg.logp_out = res["logp"].data_ptr()
+        arg.reserved = 0
+        if T:                                                    # (no step: nothing to write, and no address to hand over)
+            self._torch_call(self._lib.mt_policy_eval, C.byref(arg), commits=False)
+        del keep
+        return res
+
+    def values(self, layers_or_theta, obs, *, widths=(), hidden="tanh", out="identity", out_scale=1.0, see_pose=False):
+        """V (T, N) of a value head -- an MLP of the policy's shape whose last layer has one output -- over logged
+        observations: policy_eval(..., n_out=1)'s mean without its middle axis."""
+        return self.policy_eval(layers_or_theta, obs, n_out=1, widths=widths, hidden=hidden, out=out, out_scale=out_scale,
+                                see_pose=see_pose)["mean"][:, 0]
+
+    def gae(self, reward_log, done_log, values, last_value=None, gamma=0.99, lam=0.95, mask_after_done=False, returns=True,
+            weights=False):
+        """Generalised advantage estimation (mt_gae) from rollout_policy's logs and a critic's `values` (T, N):
+        delta_t = r_t + gamma * (0 if done_t else V_t+1) - V_t, A_t = delta_t + gamma * lam * (0 if done_t else A_t+1),
+        V_T = `last_value` (N,) or 0.  Returns a dict of (T, N) float32 device tensors: `advantages`; with returns=True
+        `returns` = A + V, the critic's regression targets; with weights=True `weights`, 1 for every step that counts.
+        mask_after_done=True (logs WITHOUT auto_reset) writes exactly 0 into all three behind an env's first done, so
+        `weights` is the coef that takes those steps out of value_grad.  One launch; stream behaviour as rollout_actions."""
+        import torch
+        T, ld = self._log_rows(reward_log, "reward_log", None, torch.int8)
+        T2, ld2 = self._log_rows(done_log, "done_log", None, torch.uint8)
+        if T2 != T or (T > 1 and ld2 != ld):
+            raise ValueError("reward_log and done_log must have the same shape and strides")
+        Tv, value_ld = self._log_rows(values, "values", None, torch.float32)
+        if Tv != T:
+            raise ValueError(f"values must have T = {T} rows")
+        g, lm = float(np.float32(gamma)), float(np.float32(lam))
+        if not (0.0 <= g <= 1.0 and 0.0 <= lm <= 1.0):
+            raise ValueError(f"gamma and lam must be in [0, 1], got {gamma!r}, {lam!r}")
+        dev = reward_log.device
+        if last_value is not None and tuple(self._flat_vector(last_value, "last_value").shape) != (self.n_envs,):
+            raise ValueError(f"last_value must have n_envs = {self.n_envs} elements")
+        names = ["advantages"] + (["returns"] if returns else []) + (["weights"] if weights else [])
+        res = {k: torch.empty((T, self.n_envs), dtype=torch.float32, device=dev) for k in names}
+        arg = L.MtGae()
+        arg.struct_size = C.sizeof(L.MtGae)
+        arg.n_steps = T
+        arg.reward_log, arg.done_log, arg.log_ld = (reward_log.data_ptr(), done_log.data_ptr(), ld) if T else (None, None, self.n_envs)
+        arg.value, arg.value_ld = (values.data_ptr() if T else None), value_ld
+        arg.last_value = last_value.data_ptr() if last_value is not None else None
+        arg.gamma, arg.lambda_ = g, lm
+        arg.adv_out, arg.adv_ld = (res["advantages"].data_ptr() if T else None), self.n_envs
+        arg.ret_out, arg.ret_ld = (res["returns"].data_ptr() if returns and T else None), self.n_envs
+        arg.weight_out, arg.weight_ld = (res["weights"].data_ptr() if weights and T else None), self.n_envs
+        arg.flags = L.GAE_MASK_AFTER_DONE if mask_after_done else 0
+        arg.reserved = 0
+        self._torch_call(self._lib.mt_gae, C.byref(arg), commits=False)
+        return res
+
+    def value_grad(self, layers_or_theta, obs, targets, coef=None, *, widths=(), hidden="tanh", out="identity", out_scale=1.0,
+                   see_pose=False, scale=1.0, grad_out=None, loss=False):
+        """The critic's regression gradient (mt_value_grad, on policy_grad's kernels): grad = scale * sum over samples of
+        coef[t, i] * (targets[t, i] - V) * dV / dtheta for the value head `layers_or_theta` (values' network), so theta +=
+        lr * grad DESCENDS the squared error; with loss=True (grad, loss), loss = scale * sum coef * (-1/2 (R - V)^2).
+        targets, coef: (T, N) float32 device tensors (gae's `returns` and `weights`); coef=None weighs every sample by 1.
+        A sample with coef == 0 or an unusable target (NaN, inf, beyond +-32768) contributes exactly nothing.  Returns grad
+        (P_v,) in flatten_policy's layout (written into `grad_out` when given).  Deterministic; two launches, no host wait;
+        the workspace is cached on the engine, apart from policy_grad's.  Stream behaviour as rollout_actions."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        arg = L.MtValueGrad()
+        keep, n_layers, n_in, p = self._policy_net_arg(arg, layers_or_theta, widths, hidden, out, see_pose, 1)
+        if not (np.isfinite(np.float32(scale)) and np.isfinite(np.float32(out_scale))):
+            raise ValueError("scale and out_scale must be finite")
+        T, obs_ld = self._log_rows(obs, "obs", n_in, torch.float32)
+        Tt, target_ld = self._log_rows(targets, "targets", None, torch.float32)
+        if coef is None:
+            coef = torch.ones((T, self.n_envs), dtype=torch.float32, device=dev)
+        Tc, coef_ld = self._log_rows(coef, "coef", None, torch.float32)
+        if not T == Tt == Tc:
+            raise ValueError(f"obs, targets and coef must have the same number of steps, got {T}, {Tt}, {Tc}")
+        if grad_out is None:
+            grad_out = torch.empty(p, dtype=torch.float32, device=dev)
+        else:
+            self._flat_vector(grad_out, "grad_out", p)
+        loss_t = torch.zeros(1, dtype=torch.float32, device=dev) if loss else None
+        arg.struct_size = C.sizeof(L.MtValueGrad)
+        arg.n_steps, arg.n_layers = T, n_layers
+        arg.hidden_act, arg.out_act = self._ACTIVATIONS[hidden], self._ACTIVATIONS[out]
+        arg.out_scale, arg.scale = float(out_scale), float(scale)
+        arg.flags = L.POLICY_SEE_POSE if see_pose else 0
+        arg.obs, arg.target, arg.coef = (obs.data_ptr(), targets.data_ptr(), coef.data_ptr()) if T else (None, None, None)
+        arg.obs_ld, arg.target_ld, arg.coef_ld = obs_ld, target_ld, coef_ld
+        arg.grad_out = grad_out.data_ptr()
+        arg.loss_out = loss_t.data_ptr() if loss else None
+        need = int(self._lib.mt_value_grad_workspace(self._h, n_layers, arg.width, arg.flags, T))
+        ws = getattr(self, "_vg_workspace", None)
+        if need and (ws is None or ws.numel() * 4 < need):
+            ws = self._vg_workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+        arg.workspace = ws.data_ptr() if need else None
+        arg.workspace_bytes = ws.numel() * 4 if need else 0
+        arg.reserved = 0
+        self._torch_call(self._lib.mt_value_grad, C.byref(arg), commits=False)
         del keep
         return (grad_out, loss_t) if loss else grad_out
 
