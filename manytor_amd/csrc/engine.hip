@@ -171,6 +171,28 @@ struct DispatchPolicy {
   // polynomial sincos kernels take over (drift: 12 rotations 3.3e-5 / 6.6e-5 in z on the 4- / 7-joint arm, 31 rotations
   // 8.6e-5 / 1.3e-4, outside the 1e-4 position tolerance)                                [tests/test_gpu_zmin.py]
   int max_recurrence_rotations = 12;
+  // sampled step launches of the code-reading prefetch kernels re-derive the pose they start from (the zero pose of a full
+  // reset, or the previous launch's action draw: kernels.h PREV) instead of loading it: 4 D of the 208 B an env-step moves,
+  // for one more Philox block per env.  Per compile-time table:
+  //   reference arm: the rows keep their 62-64 VGPRs and 8 waves per SIMD                [profiles/goal_rederive_ab.txt]
+  //   7-joint table: its launches take the prefetch kernel up to 131 072 envs only, where a launch is not HBM-bound, and
+  //   the rows go from 62-63 to 68-70 VGPRs (8 -> 7 waves per SIMD): us per step of the one-chain launch-per-step form
+  //   (MT_ROLLOUT_K=1 MT_GRAPH=0), 7 alternating passes of 400 steps, loaded -> re-derived: 70 001 envs 7.85 -> 8.21,
+  //   131 072 envs 8.27 -> 8.56 (ranges disjoint): off; MT_GOALS_REDERIVE=1 turns it on  [profiles/goal_rederive_dh7.json]
+  bool rederive_goals_ref4 = true;
+  bool rederive_goals_dh7 = false;
+  // ... and, on a multi-chain handle, by the launches of this many of its chains only (the others keep loading).  Every chain
+  // re-deriving (MT_GOALS_REDERIVE=1) takes bench.py --full's step lap of 1 M reference arms from 32.3-32.6 to 30.0-30.2 us
+  // (three alternating rounds): below the 30.54 us at which its roofline.frac, computed on a fixed 233 model bytes per env-step
+  // for 8 TB/s, reaches 1 (measured 1.012-1.018) -- a figure tests/test_bench_contract.py holds at <= 1 -- although the
+  // launches then move 196 B.  One chain of two: lap 31.6 us, frac 0.966-0.967, headline +3.2 % instead of +5.9 %.  A stop-gap:
+  // raise this to kMaxChains once the model bytes follow the kernels                       [profiles/goal_rederive_ab.txt]
+  int rederive_goals_chains = 1;
+  // ... and by launches of at most this many envs (= chains_max: beyond it a step is ONE launch of the whole batch).  The same
+  // kind of stop-gap: at 4 M arms bench.py compares the step with a stream probe of the 233-byte access shape, and the
+  // re-deriving launch, which moves less than the probe, lands on both sides of it (frac_of_achievable 0.96-1.03 in four runs,
+  // the parent 0.93-0.97; us per step 181.9 -> 179.0, -1.6 %); test_bench_contract.py holds that figure at <= 1 as well
+  int64_t rederive_goals_max_envs = 3145728;
   // rows of more than this many envs get a 1 KiB pad (rows an exact power of two apart alias onto the same channels)
   int64_t ld_pad_above = 16384;
   int ld_pad_floats = 256;
@@ -344,6 +366,17 @@ static void choose_dispatch(mt_handle h) {
     seen("MT_GROUND_COMPACT");
   }
 
+  // ---- sampled step launches re-derive the previous pose where the host knows what it is (kernels.h, PREV); 0: always load ----
+  h->goals_rederive = h->static_kind == 1 ? P.rederive_goals_ref4 : (h->static_kind == 2 ? P.rederive_goals_dh7 : false);
+  h->goals_rederive_chains = P.rederive_goals_chains;
+  h->goals_rederive_max_envs = P.rederive_goals_max_envs;
+  if (env_int("MT_GOALS_REDERIVE", &v)) {  // 1: both compile-time tables, every chain, launches of any size
+    h->goals_rederive = v != 0 && h->static_kind != 0;
+    h->goals_rederive_chains = mt_engine::kMaxChains;
+    h->goals_rederive_max_envs = INT64_MAX;
+    seen("MT_GOALS_REDERIVE");
+  }
+
   if (h->custom_frames) h->lds_table = false;
   // The schedule of launches over `envs` envs, against the thresholds of their scope
   auto schedule_for = [&](int64_t envs, int64_t split4_max, int64_t split2_max, int64_t prefetch_other_max) {
@@ -387,10 +420,11 @@ struct StepVariant {
   bool fresh = false;  // FRESH
   bool codes = false;  // CODES
   bool gc = false;     // GC: the interior poses of the ground test on dense lanes of the block (kernels.h, GroundQueue)
+  int prev = kPrevLoad;  // PREV: the pose the step starts from is loaded / the zero pose / the action draw of the step before
 };
 constexpr unsigned variant_key(const StepVariant& v) {
   return (unsigned)v.trig | (unsigned)v.lds << 3 | (unsigned)v.lanes << 4 | (unsigned)(v.pf != 0) << 7 | (unsigned)v.tt << 8 |
-         (unsigned)v.flat << 9 | (unsigned)v.fresh << 10 | (unsigned)v.codes << 11 | (unsigned)v.gc << 12;
+         (unsigned)v.flat << 9 | (unsigned)v.fresh << 10 | (unsigned)v.codes << 11 | (unsigned)v.gc << 12 | (unsigned)v.prev << 13;
 }
 
 // Every instantiation the library holds, per table type.  A row without TT exists for sampled and for staged actions
@@ -417,6 +451,13 @@ constexpr StepVariant kStaticVariants[] = {  // Ref4Table, Dh7Table
     {.gc = true}, {.pf = kPrefetch, .gc = true}, {.pf = kPrefetch, .flat = true, .gc = true},
     {.pf = 0, .tt = true, .gc = true}, {.pf = kPrefetch, .tt = true, .gc = true}, {.pf = kPrefetch, .tt = true, .flat = true, .gc = true},
     {.pf = kPrefetch, .tt = true, .codes = true, .gc = true}, {.pf = kPrefetch, .tt = true, .flat = true, .codes = true, .gc = true},
+    // the code-reading rows again, the previous pose re-derived (PREV)
+    {.pf = kPrefetch, .tt = true, .codes = true, .prev = kPrevZero}, {.pf = kPrefetch, .tt = true, .flat = true, .codes = true, .prev = kPrevZero},
+    {.pf = kPrefetch, .tt = true, .codes = true, .prev = kPrevDraw}, {.pf = kPrefetch, .tt = true, .flat = true, .codes = true, .prev = kPrevDraw},
+    {.pf = kPrefetch, .tt = true, .codes = true, .gc = true, .prev = kPrevZero},
+    {.pf = kPrefetch, .tt = true, .flat = true, .codes = true, .gc = true, .prev = kPrevZero},
+    {.pf = kPrefetch, .tt = true, .codes = true, .gc = true, .prev = kPrevDraw},
+    {.pf = kPrefetch, .tt = true, .flat = true, .codes = true, .gc = true, .prev = kPrevDraw},
 };
 #pragma clang diagnostic pop
 
@@ -456,11 +497,14 @@ static size_t ground_queue_bytes(const mt_engine* h) {  // the static LDS the GC
 //          Batch and chain launches cover whole rows, so threads past the end of the range may read on to the end of their
 //          block inside the rows (what the TT kernels do before their barrier); the single-env view does not
 //   codes  the handle's target codes are valid (engine_internal.h, codes_valid)
+//   prev   what the host knows the pose row of these envs to hold, as a PREV of kernels.h (launch_step: goals_prev); taken by
+//          the kernels that have the form (the code-reading prefetch kernels), a load for every other
 //   fresh  the first step of an episode with the deferred reset as the step kernel's own prologue (kernels.h, FRESH): the
 //          sampled-action kernels of the static tables, one env per lane.  exists = false: the caller falls back to one
 //          step of the rollout kernel
 // Cheap enough to run per launch: no allocation, no strings.
-StepPlan plan_step(const mt_engine* h, mt_engine::Scope scope, int64_t n, bool sample, bool codes, bool fresh = false) {
+StepPlan plan_step(const mt_engine* h, mt_engine::Scope scope, int64_t n, bool sample, bool codes, bool fresh = false,
+                   int prev = kPrevLoad) {
   const mt_engine::Schedule& s = h->sched[scope == mt_engine::kChain ? mt_engine::kChain : mt_engine::kBatch];
   const bool whole_rows = scope != mt_engine::kOneEnv;
   StepPlan p;
@@ -506,6 +550,7 @@ StepPlan plan_step(const mt_engine* h, mt_engine::Scope scope, int64_t n, bool s
   v.flat = v.pf && n >= h->flat_from;   // HBM-bound launches: kernels.h, LaneOffset<false>
   // the prefetch kernels read the targets as their codes while those are valid (kernels.h, CODES: 28 B per env less)
   v.codes = v.pf && v.tt && codes;
+  v.prev = v.codes ? prev : kPrevLoad;
   v.gc = ground_compacts(h, whole_rows);
   if (v.pf && v.tt) {  // see step_blocks_per_cu
     p.blocks_per_cu = step_blocks_per_cu(h, n);
@@ -521,8 +566,8 @@ void launch_variant(const StepPlan& p, hipStream_t stream, const StepArgs& args)
   if constexpr (V.lanes > 1)
     hipLaunchKernelGGL((step_split_kernel<Tbl, SAMPLE, V.lanes, V.tt>), p.grid, dim3(kBlock), p.lds_bytes, stream, args);
   else
-    hipLaunchKernelGGL((step_kernel<Tbl, SAMPLE, V.trig, V.lds, V.pf, V.tt, V.flat, V.fresh, V.codes, V.gc>), p.grid, dim3(kBlock),
-                       p.lds_bytes, stream, args);
+    hipLaunchKernelGGL((step_kernel<Tbl, SAMPLE, V.trig, V.lds, V.pf, V.tt, V.flat, V.fresh, V.codes, V.gc, V.prev>), p.grid,
+                       dim3(kBlock), p.lds_bytes, stream, args);
 }
 // ... if row I is the plan's variant (false: it is not)
 template <class Tbl, const auto& ROWS, size_t I>
@@ -582,24 +627,68 @@ void launch_trace_d(mt_handle h, const StepArgs& args, float* trace, bool sample
     hipLaunchKernelGGL((trace_kernel<D, false>), grid_for(args.n), dim3(kBlock), 0, h->stream, args, trace);
 }
 
+// May the host keep a record of what a step launch leaves in MT_F_GOALS, and trust the one it has?  Not once the row's address
+// is out (goals_exposed) or a caller was seen capturing the handle's calls (goals_foreign), not for a launch that is being captured
+// (major_base: the handle's own graphs; replays run whatever the row holds).
+static bool goals_tracked(const mt_engine* h, const StepArgs& args) {
+  return !h->goals_exposed && !h->goals_foreign && !args.major_base;
+}
+
+// What a step launch takes the pose it starts from to be: a PREV of kernels.h out of the host's record of the row
+// (engine_internal.h: GoalsRow), or -1 -- a load by a launch that leaves no record either.  The draw of step - 1 is named only
+// where the record says exactly that: the same seed, the step index right before this launch's.
+static int goals_prev(const mt_engine* h, mt_engine::Scope scope, const StepArgs& args, bool traced, bool sample, int chain) {
+  if (!sample || traced || scope == mt_engine::kOneEnv || !goals_tracked(h, args)) return -1;
+  mt_engine::GoalsRow r = h->goals_row[chain >= 0 ? chain : 0];
+  if (chain < 0)  // the whole batch: every chain's range has to be in the same state
+    for (int c = 1; c < h->chains; ++c)
+      if (h->goals_row[c].kind != r.kind || h->goals_row[c].seed != r.seed || h->goals_row[c].step != r.step) r = mt_engine::GoalsRow{};
+  // (kPolicy.rederive_goals_chains, rederive_goals_max_envs)
+  if (!h->goals_rederive || chain >= h->goals_rederive_chains || args.n > h->goals_rederive_max_envs) return kPrevLoad;
+  if (r.kind == mt_engine::GoalsRow::kZero) return kPrevZero;
+  const uint64_t seed = ((uint64_t)args.seed_hi << 32) | args.seed_lo;
+  if (r.kind == mt_engine::GoalsRow::kDraw && r.seed == seed && r.step + 1u == args.major && args.major != 0u) return kPrevDraw;
+  return kPrevLoad;
+}
+
 // One env step of the envs `args` describes (the whole batch, a chain's range, or one env of it: args_for_env), on the
 // schedule of `scope`; `trace` is the matching view of the sub-step trace buffer or NULL.
-void launch_step(mt_handle h, mt_engine::Scope scope, const StepArgs& args, float* trace, bool sample) {
+// `chain`: the chain whose range `args` is (scope kChain), -1 for the whole batch or one env of it.
+void launch_step(mt_handle h, mt_engine::Scope scope, const StepArgs& args, float* trace, bool sample, int chain = -1) {
   if (trace) MT_DISPATCH_D(h->D, launch_trace_d, h, args, trace, sample);  // first: it needs the previous pose
-  const StepPlan p = plan_step(h, scope, args.n, sample, h->codes_valid);
+  const int prev = goals_prev(h, scope, args, trace != nullptr, sample, chain);
+  const StepPlan p = plan_step(h, scope, args.n, sample, h->codes_valid, false, prev < 0 ? (int)kPrevLoad : prev);
   launch_plan(p, h->stream, args);
   h->codes_valid = p.v.codes;  // every step kernel may zero targets; only the ones that read codes zero those too
+  if (p.v.prev != kPrevLoad) ++h->goals_rederived;
+  // a sampled step of the whole range leaves its action draw as the pose (prev >= 0: a launch that runs now, with a step index
+  // the host knows); a staged action, one env of the batch, a captured launch or a traced one leave the row unknown
+  const mt_engine::GoalsRow row =
+      (prev >= 0 && sample && p.v.lanes == 1)
+          ? mt_engine::GoalsRow{mt_engine::GoalsRow::kDraw, args.major, ((uint64_t)args.seed_hi << 32) | args.seed_lo}
+          : mt_engine::GoalsRow{};
+  if (chain >= 0)
+    h->goals_row[chain] = row;
+  else
+    for (mt_engine::GoalsRow& g : h->goals_row) g = row;
 }
 
 void launch_step(mt_handle h, bool sample) { launch_step(h, mt_engine::kBatch, h->args, h->trace, sample); }
 
 // The first step of an episode with the deferred reset inside it (plan_step, fresh); false = no such kernel for this
 // handle's schedule.  `args` carries reset_seed / reset_episode / radius.
-bool launch_step_fresh(mt_handle h, mt_engine::Scope scope, const StepArgs& args) {
+bool launch_step_fresh(mt_handle h, mt_engine::Scope scope, const StepArgs& args, int chain) {
   const StepPlan p = plan_step(h, scope, args.n, true, false, true);
   if (!p.exists) return false;
   launch_plan(p, h->stream, args);
   h->codes_valid = p.v.codes;  // (false: the drawn targets are written as floats only)
+  const mt_engine::GoalsRow row = goals_tracked(h, args)  // the pose it leaves is its action draw, as after any sampled step
+                                      ? mt_engine::GoalsRow{mt_engine::GoalsRow::kDraw, args.major, ((uint64_t)args.seed_hi << 32) | args.seed_lo}
+                                      : mt_engine::GoalsRow{};
+  if (chain >= 0)
+    h->goals_row[chain] = row;
+  else
+    for (mt_engine::GoalsRow& g : h->goals_row) g = row;
   return true;
 }
 
@@ -624,7 +713,7 @@ void launch_chain(mt_handle h, const StepArgs& a0, uint32_t major0, int T, int c
   StepArgs as = args_for_range(h, a0, off, std::min(span, h->n - off));
   for (int s = 0; s < T; ++s) {
     as.major = major0 + (uint32_t)s;
-    launch_step(h, mt_engine::kChain, as, nullptr, sample);
+    launch_step(h, mt_engine::kChain, as, nullptr, sample, c);
   }
 }
 
@@ -634,7 +723,7 @@ bool launch_chain_fresh(mt_handle h, const StepArgs& a0, uint32_t major, int cha
   if (off >= h->n) return true;
   StepArgs as = args_for_range(h, a0, off, std::min(span, h->n - off));
   as.major = major;
-  return launch_step_fresh(h, mt_engine::kChain, as);
+  return launch_step_fresh(h, mt_engine::kChain, as, c);
 }
 
 // Chain c's stream (chain 0 runs on the handle's own stream).
@@ -775,6 +864,7 @@ void launch_rollout_d(mt_handle h, const StepArgs& a, int lanes, const RolloutAr
 // `lanes` per env: the rollout_lanes of the launch's scope (engine_internal.h, Schedule), or 1
 void launch_rollout(mt_handle h, const StepArgs& a, int lanes, const RolloutArgs& r, bool early = false) {
   h->codes_valid = false;  // the rollout kernels write targets as floats only
+  h->forget_goals();       // ... and leave the pose of their last step
   if (h->static_kind == 1) return early ? launch_rollout_t<Ref4Table, kPrefetch>(h, a, lanes, r) : launch_rollout_t<Ref4Table, 0>(h, a, lanes, r);
   if (h->static_kind == 2) return early ? launch_rollout_t<Dh7Table, kPrefetch>(h, a, lanes, r) : launch_rollout_t<Dh7Table, 0>(h, a, lanes, r);
   MT_DISPATCH_D(h->D, launch_rollout_d, h, a, lanes, r);
@@ -1404,6 +1494,10 @@ const char* mt_describe_dispatch(mt_handle h) {
   const StepPlan sb = batch_plan(h), sc = chain_plan(h);
   const bool multi = h->multi_k > 1 && fusable(h);
   const bool graph = h->graph_mode > 0 || (h->graph_mode < 0 && h->n <= h->graph_max);
+  const bool rederive_on = h->goals_rederive && !h->goals_exposed && !h->goals_foreign && !h->points_exposed && !h->trace;
+  auto rederives = [&](const StepPlan& p) {  // (sb: a launch of the whole batch; sc: of a chain's span)
+    return rederive_on && p.v.lanes == 1 && p.v.pf != 0 && p.v.tt && (&p == &sb ? h->n : span) <= h->goals_rederive_max_envs;
+  };
   std::string caps = "[";
   for (const BlockCap& c : P.block_caps) caps += std::string(caps.size() > 1 ? "," : "") + "[" + num(c.from) + "," + num(c.below) + "," + num(c.blocks) + "]";
   caps += "]";
@@ -1440,6 +1534,13 @@ const char* mt_describe_dispatch(mt_handle h) {
       // the ground test's interior poses on dense lanes of the block: the step launches that take it (the single-env view,
       // the rollout, tape and shoot kernels never do)
       ",\"ground_compact\":{\"enabled\":" + b(h->ground_compact) + ",\"step\":" + b(sb.v.gc) + ",\"chains\":" + b(sc.v.gc) + "}" +
+      // the pose a sampled step starts from re-derived (zero pose / the previous launch's action draw) instead of loaded: by
+      // the code-reading launches, while the host knows the row (engine_internal.h, GoalsRow).  "rederive": mt_rollout's
+      // step launches do; "step" / "chains": a launch over the whole batch / over a chain's span can
+      ",\"goals\":{\"rederive\":" + b(!multi && !graph && rederives(h->chains > 1 ? sc : sb)) + ",\"enabled\":" + b(h->goals_rederive) +
+      ",\"step\":" + b(rederives(sb)) + ",\"chains\":" + b(rederives(sc)) +
+      ",\"chains_rederiving\":" + num(rederives(sc) ? std::min(h->chains, h->goals_rederive_chains) : 0) +
+      ",\"launches_rederived\":" + num((long long)h->goals_rederived) + "}" +
       ",\"overrides\":\"" + h->overrides + "\"" +
       ",\"policy\":{\"step_split4_max\":" + num(P.step_split4_max) + ",\"step_split2_max\":" + num(P.step_split2_max) +
       ",\"prefetch_other_max\":" + num(P.prefetch_other_max) + ",\"fused_split4_max\":" + num(P.fused_split4_max) +
@@ -1449,7 +1550,9 @@ const char* mt_describe_dispatch(mt_handle h) {
       ",\"chain_prefetch_other_max\":" + num(P.chain_prefetch_other_max) + ",\"flat_from\":" + num(P.flat_from) +
       ",\"block_caps\":" + caps + ",\"multi_step_max\":" + num(P.multi_step_max) + ",\"multi_step_k\":" + num(P.multi_step_k) +
       ",\"max_recurrence_rotations\":" + num(P.max_recurrence_rotations) + ",\"ld_pad_above\":" + num(P.ld_pad_above) +
-      ",\"ld_pad_floats\":" + num(P.ld_pad_floats) + "}" +
+      ",\"ld_pad_floats\":" + num(P.ld_pad_floats) + ",\"rederive_goals_ref4\":" + b(P.rederive_goals_ref4) +
+      ",\"rederive_goals_dh7\":" + b(P.rederive_goals_dh7) + ",\"rederive_goals_chains\":" + num(P.rederive_goals_chains) +
+      ",\"rederive_goals_max_envs\":" + num(P.rederive_goals_max_envs) + "}" +
       ",\"arena_bytes\":" + num((long long)h->arena_bytes) + "}";
   return d.c_str();
 }
@@ -1459,6 +1562,7 @@ int mt_set_stream(mt_handle h, void* hip_stream) {
   MT_ENTER(h);
   MT_HIP(h, hipStreamSynchronize(h->stream));   // everything queued so far is finished before the ordering changes
   h->stream = (hipStream_t)hip_stream;          // NULL is a stream too: the legacy default stream
+  // (on a caller's stream the library's calls can be captured into the caller's graphs: mt::note_capture watches for that)
   return MT_OK;
 }
 
@@ -1472,7 +1576,7 @@ int mt_use_own_stream(mt_handle h) {
 
 int mt_sync(mt_handle h) {
   MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
-  MT_ENTER(h);  // (also: the NULL stream names the CURRENT device's default stream)
+  MT_ENTER_KEEP(h);  // (also: the NULL stream names the CURRENT device's default stream)
   MT_HIP(h, hipStreamSynchronize(h->stream));
   if (h->gather_pending) {  // a gather begun on the side stream is part of "everything queued on this handle"
     MT_HIP(h, hipStreamSynchronize(h->side_stream));
@@ -1530,6 +1634,7 @@ int mt_reset(mt_handle h, const float* points, int layout, int is_device) {
   MT_DISPATCH_D(h->D, launch_reset_d, h, h->args, 0);
   int rc = check_launch(h, "reset_kernel");
   if (rc) return rc;
+  h->goals_are(mt_engine::GoalsRow::kZero);
   if (!is_device) MT_HIP(h, hipStreamSynchronize(h->stream));  // the caller may free `points` on return
   h->is_reset = true;
   return MT_OK;
@@ -1553,6 +1658,7 @@ static int launch_reset_random(mt_handle h, uint64_t seed, uint32_t episode, int
     h->args.episode0 = episode;  // full reset: finished-episode counts restart from here
     if (!h->goals_exposed) h->args.flags |= kFlagWholeGoals;  // every env is at the zero pose after this launch
   }
+  h->forget_goals();  // (a re-arm zeroes the pose of the finished envs only; a full reset says "zero" once it is launched)
   if (per_chain) {
     int rc = fork_chains(h, h->chains);
     if (rc) return rc;
@@ -1570,6 +1676,7 @@ static int launch_reset_random(mt_handle h, uint64_t seed, uint32_t episode, int
     if (rc == MT_OK) rc = check_launch(h, "reset_kernel (per chain)");
     if (rc) return rc;
     h->codes_valid = !h->points_exposed;  // every chain's range drew its targets: codes and floats
+    h->goals_are(mt_engine::GoalsRow::kZero);  // ... and sits at the zero pose
     h->is_reset = true;
     return settle_chains(h);
   }
@@ -1578,7 +1685,10 @@ static int launch_reset_random(mt_handle h, uint64_t seed, uint32_t episode, int
   MT_DISPATCH_D(h->D, launch_reset_d, h, h->args, mode);
   rc = check_launch(h, "reset_kernel");
   if (rc) return rc;
-  if (mode == 1) h->codes_valid = !h->points_exposed;  // (a re-arm keeps them as they were: it rewrites what it draws)
+  if (mode == 1) {
+    h->codes_valid = !h->points_exposed;  // (a re-arm keeps them as they were: it rewrites what it draws)
+    h->goals_are(mt_engine::GoalsRow::kZero);
+  }
   h->is_reset = true;
   return MT_OK;
 }
@@ -1599,6 +1709,7 @@ static int reset_random_impl(mt_handle h, uint64_t seed, uint32_t episode, int m
   MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
   MT_ON_DEVICE(h, h->cfg.device);
   h->snap_valid = false;
+  note_capture(h);
   int rc = flush_pending_reset(h);  // an earlier deferred reset comes first (its last_return is what this one overwrites)
   if (rc) return rc;
   // A full reset of a handle whose mt_rollout runs k steps per launch is DEFERRED into the first launch of the next
@@ -1616,6 +1727,7 @@ static int reset_random_impl(mt_handle h, uint64_t seed, uint32_t episode, int m
     h->args.major = episode;
     h->args.episode0 = episode;
     if (!h->goals_exposed) h->args.flags |= kFlagWholeGoals;
+    h->forget_goals();  // until the reset has run: as the prologue of a step launch (launch_step_fresh) or when it is flushed
     h->reset_pending = true;
     h->pend_seed = seed;
     h->pend_episode = episode;
@@ -1741,6 +1853,7 @@ int mt_step(mt_handle h) {
   if (chains > 1) {
     MT_ON_DEVICE(h, h->cfg.device);
     h->snap_valid = false;
+    note_capture(h);
     {
       int rcf = flush_pending_reset(h);
       if (rcf) return rcf;
@@ -1811,7 +1924,7 @@ int mt_step_host(mt_handle h, const void* actions, int dtype, float* obs, int32_
 int mt_step_random(mt_handle h, uint64_t seed, uint32_t step_idx) {
   MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
   if (!h->is_reset) return fail(h, MT_ERR_STATE, "mt_step_random before mt_reset / mt_reset_random");
-  MT_ENTER(h);
+  MT_ENTER_KEEP(h);  // (launch_step keeps the record of MT_F_GOALS)
   h->args.seed_lo = (uint32_t)seed;
   h->args.seed_hi = (uint32_t)(seed >> 32);
   h->args.major = step_idx;
@@ -1879,7 +1992,7 @@ int mt_env_reset(mt_handle h, int64_t env, const float* points, uint64_t seed, u
 int mt_bad_action_count(mt_handle h, uint64_t* count) {
   MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
   MT_REQUIRE(h, count != nullptr, "count is NULL");
-  MT_ENTER(h);
+  MT_ENTER_KEEP(h);  // (MT_F_GOALS stays as it is)
   uint32_t c = 0;
   MT_HIP(h, hipMemcpyAsync(&c, h->args.bad_actions, 4, hipMemcpyDeviceToHost, h->stream));
   MT_HIP(h, hipStreamSynchronize(h->stream));
@@ -1982,6 +2095,7 @@ int mt_rollout(mt_handle h, int n_steps, uint64_t seed, uint32_t step_idx0) {
   if (n_steps > 0 && !h->is_reset) return fail(h, MT_ERR_STATE, "mt_rollout before mt_reset / mt_reset_random");
   if (n_steps == 0) return MT_OK;
   MT_ON_DEVICE(h, h->cfg.device);  // per-chain call: joins only where it has to (below)
+  note_capture(h);
   // several independent chains of launches (env ranges on separate streams) where that pays; a caller who is capturing
   // the handle's stream gets the plain single-stream sequence
   // (a call that finds a deferred reset takes the form that absorbs it even for a single step)
@@ -2085,6 +2199,7 @@ int mt_rollout(mt_handle h, int n_steps, uint64_t seed, uint32_t step_idx0) {
   if (graph) {
     const mt_engine::RolloutGraph* rg = nullptr;
     h->codes_valid = false;  // captured launches are replayed whatever the codes' state: the float kernels
+    h->forget_goals();       // ... and whatever the pose row's: they load it, and leave no record
     int rc = rollout_graph(h, n_steps, seed, chains, &rg);
     if (rc) return rc;
     if (chains > 1) {
@@ -3057,7 +3172,7 @@ int mt_mppi(mt_handle h, const struct mt_mppi* s) {
 int mt_observe(mt_handle h) {
   MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
   if (!h->is_reset) return fail(h, MT_ERR_STATE, "mt_observe before reset");
-  MT_ENTER(h);
+  MT_ENTER_KEEP(h);  // (MT_F_GOALS stays as it is)
   MT_DISPATCH_D(h->D, launch_observe_d, h);
   return check_launch(h, "observe_kernel");
 }
@@ -3065,7 +3180,7 @@ int mt_observe(mt_handle h) {
 int mt_check_done(mt_handle h) {
   MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
   if (!h->is_reset) return fail(h, MT_ERR_STATE, "mt_check_done before reset");
-  MT_ENTER(h);
+  MT_ENTER_KEEP(h);  // (MT_F_GOALS stays as it is)
   MT_DISPATCH_D(h->D, launch_check_done_d, h);
   return check_launch(h, "check_done_kernel");
 }
@@ -3100,7 +3215,7 @@ int mt_get(mt_handle h, int field, void* dst, int64_t dst_bytes, int is_device) 
   const int64_t need = env_major_bytes(h, field);
   MT_REQUIRE(h, need > 0, "unknown field (or a field this handle was created without)");
   MT_REQUIRE(h, dst_bytes == need, "dst_bytes does not match the field's env-major size");
-  MT_ENTER(h);
+  MT_ENTER_KEEP(h);  // (MT_F_GOALS stays as it is)
   const dim3 g = grid_for(h->n), b(kBlock);
   void* out = dst;
   if (!is_device) {
@@ -3325,7 +3440,7 @@ int mt_timer_lap_begin(mt_handle h) {
     int rcf = flush_pending_reset(h);  // (per chain as well while forked)
     if (rcf) return rcf;
   } else {
-    MT_ENTER(h);
+    MT_ENTER_KEEP(h);  // (MT_F_GOALS stays as it is)
   }
   mt_engine::LapRec rec{0, 1, 0, 0};
   int rc = lap_reserve(h, 2 * (size_t)mt_engine::kMaxChains);  // the whole lap's events exist before it begins

@@ -66,6 +66,31 @@ struct mt_engine {
   // while it holds; points_exposed (mt_device_ptr(MT_F_POINTS): floats may change behind the library's back) ends it for good.
   bool codes_valid = false;
   bool points_exposed = false;
+  // What the host knows MT_F_GOALS to hold, per chain range (entry c = chain c's envs; a launch over the whole batch needs
+  // all of them to agree and rewrites all of them): the zero pose after a full reset, or the action draw of (seed, step)
+  // after a sampled step launch -- a step launch that follows with the same seed and step + 1 then re-derives the pose
+  // instead of loading it (kernels.h, PREV).  Every other writer of the row leaves kUnknown: MT_ENTER forgets it for every
+  // entry point that is not known to leave the row alone (MT_ENTER_KEEP), the per-chain calls do so themselves.  goals_exposed
+  // and goals_foreign end it for good.
+  struct GoalsRow {
+    enum Kind : uint8_t { kUnknown = 0, kZero = 1, kDraw = 2 };
+    Kind kind = kUnknown;
+    uint32_t step = 0;
+    uint64_t seed = 0;
+  };
+  GoalsRow goals_row[kMaxChains];
+  void forget_goals() {
+    for (GoalsRow& g : goals_row) g = GoalsRow{};
+  }
+  void goals_are(GoalsRow::Kind kind, uint64_t seed = 0, uint32_t step = 0) {
+    for (GoalsRow& g : goals_row) g = GoalsRow{kind, step, seed};
+  }
+  bool goals_rederive = true;   // MT_GOALS_REDERIVE (0: every step launch loads the pose) and the table's entry of kPolicy
+  int goals_rederive_chains = kMaxChains;  // ... by the launches of chains 0 .. this - 1 of a multi-chain handle (kPolicy)
+  int64_t goals_rederive_max_envs = INT64_MAX;  // ... and by launches of at most this many envs (kPolicy)
+  bool goals_foreign = false;   // a call on a caller's stream was seen being captured (mt::note_capture): the replays of
+                                // that graph may write the row at any time, unseen -- the record ends for good
+  uint64_t goals_rederived = 0; // step launches that took PREV = zero / draw so far (mt_describe_dispatch: goals.launches_rederived)
   bool trig_steps = false;  // step kernels with TT: end-pose sines / cosines from the whole-degree table (static tables, sampled actions)
   int static_kind = 0;   // 0 runtime table, 1 Ref4Table, 2 Dh7Table
   mt_comm* comm = nullptr;
@@ -194,6 +219,21 @@ inline bool snapshot_trusted(mt_engine* h) {
   return st == hipStreamCaptureStatusNone;
 }
 
+// A library call that a caller is capturing into a graph of their own (possible on a caller's stream only: nobody else can
+// begin a capture on the handle's private streams) runs again at every replay, without a call: whatever it writes to
+// MT_F_GOALS is then written behind the host's record of that row (GoalsRow), which ends here for good.  Called by every
+// entry point that can write the row (MT_ENTER, mt_rollout, mt_step, the resets) and by every step launch.
+inline void note_capture(mt_engine* h) {
+  if (h->goals_foreign || h->stream == h->own_stream) return;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(h->stream, &st) != hipSuccess) {
+    (void)hipGetLastError();
+    h->goals_foreign = true;
+  } else if (st != hipStreamCaptureStatusNone) {
+    h->goals_foreign = true;
+  }
+}
+
 // engine.hip: the handle's stream waits for everything the chain streams still carry (no-op when not forked)
 int join_chains(mt_handle h);
 // engine.hip: a full reset that mt_reset_random deferred into the next mt_rollout is launched now (no-op without one)
@@ -221,10 +261,16 @@ int flush_pending_reset(mt_handle h);
 // Entry of every call that touches the handle's device state as a whole: make the handle's device current and fold the
 // chains back into the handle's stream, and launch a reset that was deferred into the next mt_rollout.  (mt_rollout and
 // mt_reset_random, which work per chain and know about deferred resets, use MT_ON_DEVICE.)
-#define MT_ENTER(h)                              \
+// What the host knew about MT_F_GOALS (GoalsRow) ends here -- the flushed reset's zero pose too: the caller may be about to
+// write the row -- unless the entry point says that it leaves the row alone or keeps the record itself: MT_ENTER_KEEP.
+// A call that is being captured on a caller's stream ends the record for good (mt::note_capture).
+#define MT_ENTER(h) MT_ENTER_IMPL(h, true)
+#define MT_ENTER_KEEP(h) MT_ENTER_IMPL(h, false)
+#define MT_ENTER_IMPL(h, forget)                 \
   MT_ON_DEVICE(h, (h)->cfg.device);              \
   do {                                           \
     (h)->snap_valid = false;                     \
+    mt::note_capture(h);                         \
     if ((h)->forked) {                           \
       int rcj__ = mt::join_chains(h);            \
       if (rcj__ != MT_OK) return rcj__;          \
@@ -233,6 +279,7 @@ int flush_pending_reset(mt_handle h);
       int rcf__ = mt::flush_pending_reset(h);    \
       if (rcf__ != MT_OK) return rcf__;          \
     }                                            \
+    if (forget) (h)->forget_goals();             \
   } while (0)
 
 // The timers' entry: the join of MT_ENTER without the rest.  A deferred reset is work of whatever FOLLOWS the timer call --

@@ -1085,10 +1085,18 @@ __device__ __forceinline__ void draw_targets_wave(uint64_t seed, uint64_t env0, 
 //   CODES  : the targets are read as their 8-byte codes (StepArgs::codes, kernels.h TargetCode) instead of the 12 bytes of
 //            their floats: 56 instead of 84 B per env at K = 7, of the 233 a step moves.  Only while the host knows the codes
 //            to match MT_F_POINTS (engine_internal.h: codes_valid); a dead target's code is zeroed with its floats.
+//   PREV   : where the pose the step starts from comes from.  A sampled step stores goals = its action, one Philox block of
+//            (seed, env, step); a full reset leaves the zero pose.  While the host knows the row to be one of the two
+//            (engine_internal.h: GoalsRow) the launch re-derives it -- kPrevDraw: draw_action of step - 1, issued where the load
+//            was, ahead of the action draw, so that the two Philox states are never live together; kPrevZero: as FRESH -- and
+//            the 4 D bytes per env stay in HBM.  The goals STORE stays: every visible field keeps its bits.  Both poses are whole
+//            degrees by construction (kFlagWholeGoals).
+enum : int { kPrevLoad = 0, kPrevZero = 1, kPrevDraw = 2 };
 template <class Tbl, bool SAMPLE, int TRIG, bool LDS, int PF = 0, bool TT = false, bool FLAT = false, bool FRESH = false,
-          bool CODES = false, bool GC = false>
+          bool CODES = false, bool GC = false, int PREV = kPrevLoad>
 __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) void step_kernel(const StepArgs a) {
   constexpr int D = Tbl::D;
+  static_assert(PREV == kPrevLoad || CODES, "the previous pose is re-derived by the code-reading kernels (the HBM-bound launches)");
   static_assert(!GC || (TRIG == 0 && !LDS && !FRESH), "the block-cooperative ground test serves the recurrence");
   static_assert(!TT || (SAMPLE && TRIG == 0 && !LDS && ActionTrigTable<Tbl>::value), "the table serves sampled actions of a static table");
   static_assert(!FRESH || TT, "the reset prologue exists for the sampled-action kernels of the static tables");
@@ -1129,8 +1137,12 @@ __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) voi
   constexpr bool kLean = D >= 6;
   MT_STAMP(a, i, 0);
   float g[D], act[D];
+  if constexpr (PREV == kPrevDraw) {
+    draw_action<D>(((uint64_t)a.seed_hi << 32) | a.seed_lo, (uint64_t)(a.env_base + i), step_no - 1u, g);
+  } else {
 #pragma unroll
-  for (int j = 0; j < D; ++j) g[j] = FRESH ? 0.f : ldr(a.goals + j * ld, o4);
+    for (int j = 0; j < D; ++j) g[j] = (FRESH || PREV == kPrevZero) ? 0.f : ldr(a.goals + j * ld, o4);
+  }
   float tx[PF ? PF : 1][3];
   uint32_t tc[CODES ? PF : 1][2];
   if constexpr (FRESH) {
@@ -1226,13 +1238,12 @@ __global__ __launch_bounds__(kBlock, (PF ? 1 : step_min_waves<Tbl, TRIG>())) voi
 
   float el[3], e[3];
   float zmin;
+  const bool prev_whole = PREV != kPrevLoad || (a.flags & kFlagWholeGoals) != 0;
   if constexpr (GC) {
-    zmin = route_kinematics_block<Tbl, TT>(t, a.S, a.inv_sm1, g, act, el, e, trig_lds, (a.flags & kFlagWholeGoals) != 0, live,
-                                           ground_q);
+    zmin = route_kinematics_block<Tbl, TT>(t, a.S, a.inv_sm1, g, act, el, e, trig_lds, prev_whole, live, ground_q);
     if (!live) return;  // behind the last barrier
   } else {
-    zmin = route_kinematics<Tbl, TRIG, false, TT>(t, a.S, a.inv_sm1, g, act, el, e, nullptr, false, trig_lds,
-                                                  (a.flags & kFlagWholeGoals) != 0);
+    zmin = route_kinematics<Tbl, TRIG, false, TT>(t, a.S, a.inv_sm1, g, act, el, e, nullptr, false, trig_lds, prev_whole);
   }
   const bool ground = zmin < 0.f;  // manytor.py:191
   if (a.zmin) str_stream(a.zmin, o4, zmin);  // MT_FLAG_DEBUG_ZMIN: wave-uniform branch on an SGPR pointer, NULL by default
