@@ -41,7 +41,7 @@ extern "C" {
 #define MT_API
 #endif
 
-#define MT_VERSION 470       /* major*10000 + minor*100 + patch */
+#define MT_VERSION 480       /* major*10000 + minor*100 + patch */
 #define MT_MAX_DOF 8
 #define MT_MAX_TARGETS 32
 #define MT_MAX_RETURN_RING 64
@@ -781,6 +781,64 @@ MT_API int mt_set_episode_base(mt_handle h, uint32_t episode0);
  * joint angles may change behind its back: from then on it never assumes them to be whole degrees (the table look-up
  * the sampled-action kernels use for the pose a step starts from is replaced by the computed sines / cosines). */
 MT_API int mt_device_ptr(mt_handle h, int field, void** ptr, int64_t* rows, int64_t* ld, int* dtype);
+
+/* Inverse kinematics of the pickup frame: which joint angles put the hand on that point?  Not in the reference (it has no
+ * solver; its targets are met by sampled actions, test_multi.py:19-21).
+ * The driven point p(q) is the origin of the frame the pickup test uses (mt_config.ee_frame, resolved as everywhere: for
+ * the built-in tables the frame after all D joints).  MT_ERR_UNSUPPORTED when ee_frame resolves to the origin row: that
+ * point does not move.  With joint j at theta_j = q_j + off_j, z_j and o_j the Z axis and the origin of the frame BEFORE
+ * joint j (z_0 = (0, 0, 1), o_0 = 0), column j of the position Jacobian is z_j x (p - o_j) per radian for every joint up to
+ * the last one the driven frame depends on and exactly 0 for later joints.
+ *
+ * mt_jacobian: jac_out[(3 j + a) * jac_ld + i] = d p_a / d q_j of env i per DEGREE (the per-radian column times pi / 180),
+ * pos_out[a * pos_ld + i] = p_a (optional).  angles is DEVICE (D, angles_ld) f32 degrees, or NULL: the resident pose
+ * MT_F_GOALS (MT_ERR_STATE before a reset).  One launch on the handle's stream; nothing resident is written.
+ *
+ * mt_ik: `iters` damped-least-squares iterations per env in ONE launch.  One iteration, J per radian at the current q:
+ *   e = x - p(q);  A = J J^T + damping^2 I_3;  y = A^-1 e;  dq = (180 / pi) J^T y;
+ *   m = max_j |dq_j|;  if m > max_step_deg: dq *= max_step_deg / m;  q += dq
+ * in fp32 with a fixed operation order: an env's result depends on its own inputs only (not on the batch, its neighbours
+ * or the row pitches), and two calls give the same bits.
+ * Early stop (tol > 0): an env whose box residual max(|e_x|, |e_y|, |e_z|) -- the pickup test's metric -- is <= tol BEFORE
+ * an iteration takes no further step; its angles are, bit for bit, those of a call with that many iterations.
+ * Target: x = target[a * target_ld + i], or with target NULL the alive target of env i with the smallest squared Euclidean
+ * distance from p at the START pose (the lowest index wins a tie), read from MT_F_POINTS and the alive mask;
+ * index_out[i] names it.  An env without an alive target gets index -1, its start angles bit for bit, residual 0, 0 steps.
+ * Start: start[j * start_ld + i], or with start NULL the resident pose MT_F_GOALS.
+ * An env with a non-finite target coordinate or an unusable start angle (NaN, +-inf, beyond +-32768 degrees) is held the
+ * same way with residual NaN; no other env's outputs change.
+ * Results: angles_out[j * angles_ld + i] (the layout of MT_F_ACTIONS and of one step of mt_policy.action_log) is the final
+ * q -- with MT_IK_WRAP mapped into [-180, 180), the reference's action domain (manytor.py:216); without it continuous
+ * from the start pose, the short route for mt_step's interpolation -- residual_out[i] the box residual at the angles
+ * written (one more forward pass), iters_out[i] the steps taken.  Any output may be NULL; all NULL without MT_IK_STAGE is
+ * refused.  MT_IK_STAGE also writes the angles to MT_F_ACTIONS: the next mt_step executes them, exactly as after
+ * mt_set_actions with the same angles.  Nothing else resident is written.
+ * Everything the host can see is screened before any launch (MT_ERR_INVALID_ARG; every ld >= n_envs; index_out with an
+ * explicit target); MT_ERR_STATE before a reset whenever the call reads or stages resident state (target NULL, start
+ * NULL, MT_IK_STAGE).  One launch on the handle's stream, no allocation, no host wait: legal under stream capture. */
+#define MT_IK_STAGE 0x1u       /* also write the angles to MT_F_ACTIONS */
+#define MT_IK_WRAP  0x2u       /* angles mapped into [-180, 180) */
+#define MT_IK_MAX_ITERS 255
+struct mt_ik {             /* as with mt_cem, the type is always written `struct mt_ik` */
+  int32_t struct_size;     /* = sizeof(struct mt_ik), checked */
+  int32_t iters;           /* 1..MT_IK_MAX_ITERS */
+  float damping;           /* lambda, finite, > 0, in length units */
+  float max_step_deg;      /* finite, > 0: the largest joint move of one iteration */
+  float tol;               /* finite, >= 0: box residual at which an env stops; 0 = never stop early */
+  uint32_t flags;          /* MT_IK_* */
+  const float* target; int64_t target_ld;   /* DEVICE (3, target_ld) x / y / z, or NULL: each env's nearest alive target */
+  const float* start;  int64_t start_ld;    /* DEVICE (D, start_ld) degrees, or NULL: MT_F_GOALS */
+  float* angles_out;   int64_t angles_ld;   /* DEVICE (D, angles_ld) or NULL */
+  float* residual_out;     /* DEVICE f32 (n_envs,) or NULL */
+  int32_t* iters_out;      /* DEVICE i32 (n_envs,) or NULL */
+  int32_t* index_out;      /* DEVICE i32 (n_envs,) or NULL; nearest-target mode only */
+  uint64_t reserved;       /* must be 0 */
+};
+MT_API int mt_ik(mt_handle h, const struct mt_ik* s);
+/* (angles, jac_out and pos_out are DEVICE f32 rows handed over as void*, like mt_sample_plans' block: device memory cannot
+ * be screened on the host.  An unusable angle gives that env's own outputs unspecified values and touches nothing else.) */
+MT_API int mt_jacobian(mt_handle h, const void* angles, int64_t angles_ld, void* jac_out, int64_t jac_ld, void* pos_out,
+                       int64_t pos_ld);
 
 /* ---- multi-GPU: the one exchange of the path ---------------------------------------------------
  * Envs share nothing, so stepping needs no collective.  What is exchanged is what test_multi.py:32 prints: the

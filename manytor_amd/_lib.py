@@ -445,6 +445,33 @@ class MtValueGrad(C.Structure):
 
 GAE_MASK_AFTER_DONE = 0x1
 
+
+class MtIk(C.Structure):
+    """struct mt_ik of include/manytor_hip.h: the argument block of mt_ik."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("iters", C.c_int32),
+        ("damping", C.c_float),
+        ("max_step_deg", C.c_float),
+        ("tol", C.c_float),
+        ("flags", C.c_uint32),
+        ("target", C.c_void_p),
+        ("target_ld", C.c_int64),
+        ("start", C.c_void_p),
+        ("start_ld", C.c_int64),
+        ("angles_out", C.c_void_p),
+        ("angles_ld", C.c_int64),
+        ("residual_out", C.c_void_p),
+        ("iters_out", C.c_void_p),
+        ("index_out", C.c_void_p),
+        ("reserved", C.c_uint64),
+    ]
+
+
+IK_STAGE = 0x1
+IK_WRAP = 0x2
+IK_MAX_ITERS = 255
+
 _HANDLE = C.c_void_p
 
 # name -> (restype, argtypes); exactly the prototypes of include/manytor_hip.h
@@ -489,6 +516,8 @@ PROTOTYPES = {
     "mt_gae": (C.c_int, [_HANDLE, C.POINTER(MtGae)]),
     "mt_value_grad": (C.c_int, [_HANDLE, C.POINTER(MtValueGrad)]),
     "mt_value_grad_workspace": (C.c_size_t, [_HANDLE, C.c_int, C.POINTER(C.c_int32), C.c_uint32, C.c_int]),
+    "mt_ik": (C.c_int, [_HANDLE, C.POINTER(MtIk)]),
+    "mt_jacobian": (C.c_int, [_HANDLE, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "mt_observe": (C.c_int, [_HANDLE]),
     "mt_check_done": (C.c_int, [_HANDLE]),
     "mt_get": (C.c_int, [_HANDLE, C.c_int, C.c_void_p, C.c_int64, C.c_int]),

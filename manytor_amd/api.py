@@ -266,6 +266,24 @@ class Multienv:
         self._engine.sample_actions(self.seed, self._step_idx)
         return DEVICE_ACTIONS
 
+    def reach_actions(self, **kw):
+        """A scripted expert in action_sample's place: for every env the joint angles that carry the pickup frame to its
+        nearest alive target (StepEngine.ik, which documents the keywords: iters, damping, max_step, tol, wrap), in the
+        shape action_sample returns -- numpy mode: per-env lists of floats for small N, an (N, D) float32 array otherwise;
+        device mode: the angles are staged in the device action buffer and ``self.DEVICE_ACTIONS`` is returned.  So
+        ``env.step(env.reach_actions())`` works in the reference's loop.  An env without an alive target keeps its pose."""
+        for name in ("stage", "targets", "start"):
+            if name in kw:
+                raise TypeError(f"reach_actions() sets {name!r} itself")
+        e = self._engine
+        if self.rng != "numpy":
+            e.ik(stage=True, angles=False, residual=False, index=False, **kw)
+            return DEVICE_ACTIONS
+        res = e.ik(residual=False, index=False, **kw)
+        e.sync()
+        a = np.ascontiguousarray(res["angles"].cpu().numpy().T)
+        return [list(row) for row in a] if self._materialize else a
+
     def step(self, action):
         """manytor.py:115-122 -> (obs2_list, reward_list, done_list)."""
         streaming = self.rendering and self._viewer is not None

@@ -831,6 +831,35 @@ void launch_joints_d(mt_handle h, float* out) {
   hipLaunchKernelGGL((joints_kernel<D>), grid_for(h->n), dim3(kBlock), 0, h->stream, h->args, out);
 }
 
+// ik_kernel / jacobian_kernel with the handle's table: the compile-time table it matched, else the runtime table with the
+// runtime pickup frame.
+template <class Tbl>
+void launch_ik_t(mt_handle h, const IkArgs& r) {
+  hipLaunchKernelGGL((ik_kernel<Tbl>), grid_for(r.n), dim3(kBlock), 0, h->stream, r);
+}
+template <int D>
+void launch_ik_d(mt_handle h, const IkArgs& r) {
+  launch_ik_t<RtTableF<D>>(h, r);
+}
+void launch_ik(mt_handle h, const IkArgs& r) {
+  if (h->static_kind == 1) return launch_ik_t<Ref4Table>(h, r);
+  if (h->static_kind == 2) return launch_ik_t<Dh7Table>(h, r);
+  MT_DISPATCH_D(h->D, launch_ik_d, h, r);
+}
+template <class Tbl>
+void launch_jacobian_t(mt_handle h, const JacobianArgs& r) {
+  hipLaunchKernelGGL((jacobian_kernel<Tbl>), grid_for(r.n), dim3(kBlock), 0, h->stream, r);
+}
+template <int D>
+void launch_jacobian_d(mt_handle h, const JacobianArgs& r) {
+  launch_jacobian_t<RtTableF<D>>(h, r);
+}
+void launch_jacobian(mt_handle h, const JacobianArgs& r) {
+  if (h->static_kind == 1) return launch_jacobian_t<Ref4Table>(h, r);
+  if (h->static_kind == 2) return launch_jacobian_t<Dh7Table>(h, r);
+  MT_DISPATCH_D(h->D, launch_jacobian_d, h, r);
+}
+
 // The rollout kernels on the envs `a` describes (the whole batch or a chain's 256-aligned range), `split` lanes per env.
 // RPF (kernels.h): the prologue that requests everything up front and runs the first step under the loads -- for the short
 // launches of mt_rollout's multi-step form, compile-time tables only (the long fused launches keep RPF = 0).
@@ -3183,6 +3212,81 @@ int mt_check_done(mt_handle h) {
   MT_ENTER_KEEP(h);  // (MT_F_GOALS stays as it is)
   MT_DISPATCH_D(h->D, launch_check_done_d, h);
   return check_launch(h, "check_done_kernel");
+}
+
+// ---- inverse kinematics -------------------------------------------------------------------------
+int mt_jacobian(mt_handle h, const void* angles, int64_t angles_ld, void* jac_out, int64_t jac_ld, void* pos_out,
+                int64_t pos_ld) {
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  MT_REQUIRE(h, jac_out != nullptr, "mt_jacobian: jac_out is NULL");
+  MT_REQUIRE(h, angles == nullptr || angles_ld >= h->n, "mt_jacobian: angles_ld is smaller than n_envs");
+  MT_REQUIRE(h, jac_ld >= h->n, "mt_jacobian: jac_ld is smaller than n_envs");
+  MT_REQUIRE(h, pos_out == nullptr || pos_ld >= h->n, "mt_jacobian: pos_ld is smaller than n_envs");
+  if (h->args.dh.fe == 0) return fail(h, MT_ERR_UNSUPPORTED, "mt_jacobian: ee_frame is the origin row, which no joint moves");
+  if (!angles && !h->is_reset) return fail(h, MT_ERR_STATE, "mt_jacobian of the resident pose before reset");
+  MT_ENTER_KEEP(h);  // (MT_F_GOALS stays as it is)
+  JacobianArgs r{};
+  r.angles = angles ? static_cast<const float*>(angles) : h->args.goals;
+  r.angles_ld = angles ? angles_ld : h->ld;
+  r.jac = static_cast<float*>(jac_out);
+  r.jac_ld = jac_ld;
+  r.pos = static_cast<float*>(pos_out);
+  r.pos_ld = pos_ld;
+  r.n = h->n;
+  r.dh = h->args.dh;
+  launch_jacobian(h, r);
+  return check_launch(h, "jacobian_kernel");
+}
+
+// Staging (MT_IK_STAGE) needs no bookkeeping of its own: MT_F_ACTIONS has no host-side record (only MT_F_GOALS and
+// MT_F_POINTS have: GoalsRow, codes_valid, the exposure flags), and the mt_step that executes staged actions is what ends
+// kFlagWholeGoals and the record of the pose -- whoever staged them.  The call enters as mt_observe does, which folds the
+// chains back, so the write is ordered ahead of a per-chain mt_step as well.
+int mt_ik(mt_handle h, const struct mt_ik* s) {
+  MT_REQUIRE(h, s != nullptr, "ik is NULL");  // (the struct first: its size is checked with or without a handle)
+  MT_REQUIRE(h, s->struct_size == (int32_t)sizeof(struct mt_ik), "mt_ik.struct_size does not match this library");
+  MT_REQUIRE(h, s->reserved == 0, "mt_ik.reserved must be 0");
+  MT_REQUIRE(h, (s->flags & ~(uint32_t)(MT_IK_STAGE | MT_IK_WRAP)) == 0, "mt_ik.flags: unknown MT_IK_* flag");
+  MT_REQUIRE(h, s->iters >= 1 && s->iters <= MT_IK_MAX_ITERS, "mt_ik.iters must be 1.." + std::to_string(MT_IK_MAX_ITERS));
+  // (bit patterns: the build is -ffinite-math-only)
+  MT_REQUIRE(h, first_unusable(&s->damping, 1, kMaxFiniteBits) < 0 && s->damping > 0.f, "mt_ik.damping must be finite and > 0");
+  MT_REQUIRE(h, first_unusable(&s->max_step_deg, 1, kMaxFiniteBits) < 0 && s->max_step_deg > 0.f, "mt_ik.max_step_deg must be finite and > 0");
+  MT_REQUIRE(h, first_unusable(&s->tol, 1, kMaxFiniteBits) < 0 && s->tol >= 0.f, "mt_ik.tol must be finite and >= 0");
+  const bool stage = (s->flags & MT_IK_STAGE) != 0;
+  MT_REQUIRE(h, stage || s->angles_out || s->residual_out || s->iters_out || s->index_out, "mt_ik: no output and no MT_IK_STAGE");
+  MT_REQUIRE(h, s->target == nullptr || s->index_out == nullptr, "mt_ik.index_out is for the nearest-target mode (target NULL)");
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  const int64_t n = h->n;
+  MT_REQUIRE(h, s->target == nullptr || s->target_ld >= n, "mt_ik.target_ld is smaller than n_envs");
+  MT_REQUIRE(h, s->start == nullptr || s->start_ld >= n, "mt_ik.start_ld is smaller than n_envs");
+  MT_REQUIRE(h, s->angles_out == nullptr || s->angles_ld >= n, "mt_ik.angles_ld is smaller than n_envs");
+  if (h->args.dh.fe == 0) return fail(h, MT_ERR_UNSUPPORTED, "mt_ik: ee_frame is the origin row, which no joint moves");
+  if ((!s->target || !s->start || stage) && !h->is_reset) return fail(h, MT_ERR_STATE, "mt_ik reads or stages resident state before reset");
+  MT_ENTER_KEEP(h);  // (MT_F_GOALS stays as it is)
+  IkArgs r{};
+  r.start = s->start ? s->start : h->args.goals;
+  r.start_ld = s->start ? s->start_ld : h->ld;
+  r.target = s->target;
+  r.target_ld = s->target_ld;
+  r.points = h->args.points;
+  r.alive = h->args.alive;
+  r.ld = h->ld;
+  r.angles = s->angles_out;
+  r.angles_ld = s->angles_ld;
+  r.stage = stage ? h->args.actions : nullptr;
+  r.residual = s->residual_out;
+  r.steps = s->iters_out;
+  r.index = s->index_out;
+  r.n = n;
+  r.K = h->K;
+  r.iters = s->iters;
+  r.wrap = (s->flags & MT_IK_WRAP) ? 1u : 0u;
+  r.lambda2 = s->damping * s->damping;  // one fp32 product
+  r.max_step = s->max_step_deg;
+  r.tol = s->tol;
+  r.dh = h->args.dh;
+  launch_ik(h, r);
+  return check_launch(h, "ik_kernel");
 }
 
 // ---- getters / setters ------------------------------------------------------------------------

@@ -4035,6 +4035,255 @@ __global__ __launch_bounds__(kBlock) void mppi_kernel(const StepArgs a, const Mp
 }
 
 // ---------------------------------------------------------------------------
+// Inverse kinematics of the pickup frame (mt_jacobian, mt_ik): the analytic position Jacobian and a fixed number of
+// damped-least-squares iterations, one env per lane.  Not in the reference: it has no solver.
+//
+// The driven point p is the origin of the pickup frame (Tbl: the frame after all D joints; RtTableF: row fe of
+// joints_coordinates, fe >= 1 -- the host refuses the origin row).  With z_j, o_j the Z axis and the origin of the frame
+// BEFORE joint j, column j of the Jacobian is z_j x (p - o_j) per radian for every joint the frame depends on and exactly 0
+// behind it.  One forward pass keeps the 6 D floats of (z_j, o_j) in registers and forms the columns once p is known.
+// The chain is chain_all's, operation for operation, so p rounds as the frame origins do everywhere else; with a
+// compile-time table the products with 0 / +-1 fall away and joint 0 never enters a z (z_0 is the constant (0, 0, 1)).
+// ---------------------------------------------------------------------------
+constexpr float kRadPerDeg = 0.017453292519943295f;
+constexpr float kDegPerRad = 57.29577951308232f;
+
+template <class Tbl, bool JAC>
+__device__ __forceinline__ void ik_forward(const float (&q)[Tbl::D], const Tbl& t, float (&p)[3], float (&J)[3][Tbl::D]) {
+  constexpr int D = Tbl::D;
+  float X[3] = {1.f, 0.f, 0.f}, Y[3] = {0.f, 1.f, 0.f}, Z[3] = {0.f, 0.f, 1.f};
+  float o[3] = {0.f, 0.f, 0.f};
+  float zj[D][3], oj[D][3];
+  if constexpr (Tbl::kFrames) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) p[a] = 0.f;
+  }
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    float s, c;
+    sincos_deg_off(q[j], t.off(j), s, c);
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      zj[j][a] = Z[a];
+      oj[j][a] = o[a];
+      const float nx = pfma(X[a], c, pmul(Y[a], s));
+      const float tt = pfma(Y[a], c, -pmul(X[a], s));
+      o[a] = pfma(t.a(j), nx, pfma(t.d(j), Z[a], o[a]));
+      X[a] = nx;
+      Y[a] = pfma(tt, t.ca(j), pmul(Z[a], t.sa(j)));
+      Z[a] = pfma(Z[a], t.ca(j), -pmul(tt, t.sa(j)));
+      if constexpr (Tbl::kFrames) p[a] = (j >= 1 && j == t.fe()) ? o[a] : p[a];
+    }
+  }
+  if constexpr (!Tbl::kFrames) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) p[a] = o[a];
+  }
+  if constexpr (JAC) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      const float r0 = p[0] - oj[j][0], r1 = p[1] - oj[j][1], r2 = p[2] - oj[j][2];
+      float c0 = pfma(zj[j][1], r2, -pmul(zj[j][2], r1));
+      float c1 = pfma(zj[j][2], r0, -pmul(zj[j][0], r2));
+      float c2 = pfma(zj[j][0], r1, -pmul(zj[j][1], r0));
+      if constexpr (Tbl::kFrames) {  // a joint behind the driven frame does not move it
+        const bool drives = j <= t.fe();
+        c0 = drives ? c0 : 0.f;
+        c1 = drives ? c1 : 0.f;
+        c2 = drives ? c2 : 0.f;
+      }
+      J[0][j] = c0;
+      J[1][j] = c1;
+      J[2][j] = c2;
+    }
+  }
+}
+
+struct JacobianArgs {
+  const float* angles;  // [D][angles_ld] degrees
+  int64_t angles_ld;
+  float* jac;           // [3 D][jac_ld]: row 3 j + a = d p_a / d q_j per DEGREE
+  int64_t jac_ld;
+  float* pos;           // [3][pos_ld] or NULL: p
+  int64_t pos_ld;
+  int64_t n;
+  DhConst dh;
+};
+
+template <class Tbl>
+__global__ __launch_bounds__(kBlock) void jacobian_kernel(const JacobianArgs a) {
+  constexpr int D = Tbl::D;
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;  // 32-bit lane offset: rows are addressed as uniform base + i
+  if (i >= a.n) return;
+  const Tbl t = TableMaker<Tbl>::make(a.dh);
+  float q[D], p[3], J[3][D];
+#pragma unroll
+  for (int j = 0; j < D; ++j) q[j] = (a.angles + j * a.angles_ld)[i];
+  ik_forward<Tbl, true>(q, t, p, J);
+#pragma unroll
+  for (int j = 0; j < D; ++j)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) (a.jac + (int64_t)(3 * j + c) * a.jac_ld)[i] = J[c][j] * kRadPerDeg;
+  if (a.pos) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) (a.pos + c * a.pos_ld)[i] = p[c];
+  }
+}
+
+// mt_ik.  Per iteration, with the per-radian J at the current pose:
+//   e = x - p;  A = J J^T + lambda^2 I;  y = A^-1 e;  dq = (180 / pi) J^T y;  m = max |dq_j|;  m > max_step: dq *= max_step / m
+// A is symmetric positive definite with every pivot >= lambda^2, so it is factored as L D L^T without pivoting: three
+// divisions, and no cancellation of the size the adjugate's 2 x 2 minors carry when J J^T is close to singular.
+// Every product is written as an fma chain in a fixed order (the build does not contract), so an env's result is a function
+// of its own inputs alone: batch size, neighbours and the launch shape change no bit.
+// An env freezes when its box residual max |e_a| is <= tol BEFORE an iteration (tol > 0 only): it takes no further step,
+// which leaves exactly the angles of a run with fewer iterations; a wave whose lanes are all frozen leaves the loop -- the
+// ballot is the kernel's only cross-lane operation.  No LDS, no atomics.
+// Held envs (angles = start bit for bit, 0 steps): an unusable start angle or a non-finite target (residual NaN), and in
+// nearest mode an env without an alive target (index -1, residual 0).  They compute on the zero pose and re-read their start.
+struct IkArgs {
+  const float* start;   // [D][start_ld] degrees (the caller's, or MT_F_GOALS)
+  int64_t start_ld;
+  const float* target;  // [3][target_ld], or NULL: each env's nearest alive target
+  int64_t target_ld;
+  const float* points;  // resident rows, read in nearest mode only: [3K][ld]
+  const uint32_t* alive;
+  int64_t ld;
+  float* angles;        // [D][angles_ld] or NULL
+  int64_t angles_ld;
+  float* stage;         // MT_F_ACTIONS ([D][ld]) or NULL
+  float* residual;      // [n] or NULL
+  int32_t* steps;       // [n] or NULL
+  int32_t* index;       // [n] or NULL (nearest mode)
+  int64_t n;
+  int32_t K, iters;
+  uint32_t wrap;
+  float lambda2, max_step, tol;
+  DhConst dh;
+};
+
+template <class Tbl>
+__global__ __launch_bounds__(kBlock) void ik_kernel(const IkArgs a) {
+  constexpr int D = Tbl::D;
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;  // 32-bit lane offset: rows are addressed as uniform base + i
+  if (i >= a.n) return;
+  const Tbl t = TableMaker<Tbl>::make(a.dh);
+  float q[D], p[3], J[3][D], x[3] = {0.f, 0.f, 0.f};
+  bool poisoned = false;
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    q[j] = (a.start + j * a.start_ld)[i];
+    poisoned |= unusable_angle(q[j]);
+  }
+  if (poisoned) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) q[j] = 0.f;
+  }
+  int idx = -1;
+  if (a.target) {
+    // read as words: the build is -ffinite-math-only, under which a float that is TESTED for NaN may be assumed not to be one
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(a.target);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const uint32_t w = (words + c * a.target_ld)[i];
+      poisoned |= (w & 0x7F800000u) == 0x7F800000u;
+      x[c] = __uint_as_float(w);
+    }
+  } else {
+    ik_forward<Tbl, false>(q, t, p, J);
+    const uint32_t am = poisoned ? 0u : a.alive[i];
+    float best = 0.f;
+    for (int k = 0; k < a.K; ++k) {
+      if (!((am >> k) & 1u)) continue;
+      const float* row = a.points + (int64_t)(3 * k) * a.ld;
+      const float tx = row[i], ty = (row + a.ld)[i], tz = (row + 2 * a.ld)[i];
+      const float dx = tx - p[0], dy = ty - p[1], dz = tz - p[2];
+      const float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
+      if (idx < 0 || d2 < best) {  // (ascending k and a strict compare: the lowest index wins a tie)
+        best = d2;
+        idx = k;
+        x[0] = tx;
+        x[1] = ty;
+        x[2] = tz;
+      }
+    }  // (resident targets are finite: every way into MT_F_POINTS is screened)
+  }
+  const bool held = poisoned || (!a.target && idx < 0);
+  if (poisoned) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) x[c] = 0.f;
+  }
+  bool frozen = held;
+  int steps = 0;
+  for (int it = 0; it < a.iters; ++it) {
+    if (__ballot(!frozen) == 0ull) break;  // (wave-uniform)
+    ik_forward<Tbl, true>(q, t, p, J);
+    const float e0 = x[0] - p[0], e1 = x[1] - p[1], e2 = x[2] - p[2];
+    const float box = fmaxf(fmaxf(fabsf(e0), fabsf(e1)), fabsf(e2));
+    frozen |= (a.tol > 0.f) && (box <= a.tol);
+    float a00 = a.lambda2, a11 = a.lambda2, a22 = a.lambda2, a01 = 0.f, a02 = 0.f, a12 = 0.f;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      a00 = pfma(J[0][j], J[0][j], a00);
+      a01 = pfma(J[0][j], J[1][j], a01);
+      a02 = pfma(J[0][j], J[2][j], a02);
+      a11 = pfma(J[1][j], J[1][j], a11);
+      a12 = pfma(J[1][j], J[2][j], a12);
+      a22 = pfma(J[2][j], J[2][j], a22);
+    }
+    // A = L D L^T, then L w = e, D v = w, L^T y = v
+    const float i0 = 1.0f / a00;
+    const float l10 = a01 * i0, l20 = a02 * i0;
+    const float i1 = 1.0f / __builtin_fmaf(-l10, a01, a11);
+    const float u12 = __builtin_fmaf(-l20, a01, a12);
+    const float l21 = u12 * i1;
+    const float i2 = 1.0f / __builtin_fmaf(-l21, u12, __builtin_fmaf(-l20, a02, a22));
+    const float w1 = __builtin_fmaf(-l10, e0, e1);
+    const float w2 = __builtin_fmaf(-l21, w1, __builtin_fmaf(-l20, e0, e2));
+    const float y2 = w2 * i2;
+    const float y1 = __builtin_fmaf(-l21, y2, w1 * i1);
+    const float y0 = __builtin_fmaf(-l20, y2, __builtin_fmaf(-l10, y1, e0 * i0));
+    float dq[D], m = 0.f;
+#pragma unroll
+    for (int j = 0; j < D; ++j) {
+      dq[j] = kDegPerRad * pfma(J[2][j], y2, pfma(J[1][j], y1, pmul(J[0][j], y0)));
+      m = fmaxf(m, fabsf(dq[j]));
+    }
+    const float scale = (m > a.max_step) ? a.max_step / m : 1.0f;  // (m > max_step > 0: never a division by 0)
+    if (!frozen) {
+#pragma unroll
+      for (int j = 0; j < D; ++j) q[j] = __builtin_fmaf(dq[j], scale, q[j]);
+      ++steps;
+    }
+  }
+  float res;
+  if (held) {
+#pragma unroll
+    for (int j = 0; j < D; ++j) q[j] = (a.start + j * a.start_ld)[i];
+    res = poisoned ? __uint_as_float(0x7FC00000u) : 0.f;
+  } else {
+    if (a.wrap) {  // into [-180, 180): q - 360 k is exact in fp32 (the result is a smaller multiple of q's ulp)
+#pragma unroll
+      for (int j = 0; j < D; ++j) {
+        float r = __builtin_fmaf(__builtin_rintf(q[j] * (1.0f / 360.0f)), -360.0f, q[j]);
+        r = (r >= 180.0f) ? r - 360.0f : r;
+        q[j] = (r < -180.0f) ? r + 360.0f : r;
+      }
+    }
+    ik_forward<Tbl, false>(q, t, p, J);
+    res = fmaxf(fmaxf(fabsf(x[0] - p[0]), fabsf(x[1] - p[1])), fabsf(x[2] - p[2]));
+  }
+#pragma unroll
+  for (int j = 0; j < D; ++j) {
+    if (a.angles) (a.angles + j * a.angles_ld)[i] = q[j];
+    if (a.stage) (a.stage + j * a.ld)[i] = q[j];
+  }
+  if (a.residual) a.residual[i] = res;
+  if (a.steps) a.steps[i] = steps;
+  if (a.index) a.index[i] = idx;
+}
+
+// ---------------------------------------------------------------------------
 // get_observations() at the current pose (manytor.py:141-153).
 // ---------------------------------------------------------------------------
 template <int D>

@@ -1309,6 +1309,121 @@ class StepEngine:
         self._torch_call(self._lib.mt_mppi, C.byref(arg), commits=bool(commit and T))
         return out
 
+    # ---- inverse kinematics: the Jacobian of the pickup frame and a damped-least-squares solver ----------------------------
+    def _ik_rows(self, t, name, rows):
+        """`rows` rows of per-env floats as the library reads them -> (float32 device tensor of shape (rows, N), ld).  A CUDA
+        float32 (rows, N) tensor with unit env stride and a row pitch >= N -- a [..., :N] view of a wider buffer included --
+        goes in zero-copy; an (N, rows) tensor, a numpy array or nested lists of either shape become a contiguous copy."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        n = self.n_envs
+        if _is_torch_tensor(t):
+            t = t.detach()
+            if t.dim() == 2 and tuple(t.shape) == (rows, n) and t.dtype == torch.float32 and t.device == dev:
+                _, ld = self._log_rows(t, name, None, torch.float32)
+                return t, ld
+        else:
+            t = torch.from_numpy(np.array(t, dtype=np.float32))
+        if t.dim() != 2 or tuple(t.shape) not in ((rows, n), (n, rows)):
+            raise ValueError(f"{name} must be ({rows}, {n}) or ({n}, {rows}), got {tuple(t.shape)}")
+        if tuple(t.shape) != (rows, n):
+            t = t.t()
+        return t.to(device=dev, dtype=torch.float32).contiguous(), n
+
+    def _ik_vector(self, t, name, dtype):
+        import torch
+        dev = torch.device("cuda", self.device)
+        if (not _is_torch_tensor(t) or t.dtype != dtype or t.device != dev or tuple(t.shape) != (self.n_envs,)
+                or (self.n_envs > 1 and t.stride(0) != 1)):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape ({self.n_envs},) on {dev}")
+        return t
+
+    def jacobian(self, angles=None, out=None, position=False):
+        """The position Jacobian of the pickup frame (mt_jacobian) as a (3, D, N) float32 device tensor: [a, j, i] =
+        d p_a / d q_j of env i per DEGREE -- column j is z_j x (p - o_j) * pi / 180, exactly 0 for a joint behind the
+        driven frame (ee_frame).  angles: (D, N) degrees (read in place when a float32 device tensor, [..., :N] views
+        included) or (N, D); None = the resident pose.  out: a (3, D, N) tensor to write into whose memory runs (D, 3, ld),
+        e.g. buf.view(D, 3, ld)[..., :N].permute(1, 0, 2).  position=True returns (jacobian, p) with p (3, N), the driven
+        point.  One launch; stream behaviour as rollout_actions; nothing resident is written."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        n, d = self.n_envs, self.dof
+        ang, ang_ld = (None, n) if angles is None else self._ik_rows(angles, "angles", d)
+        if out is None:
+            out = torch.empty((d, 3, n), dtype=torch.float32, device=dev).permute(1, 0, 2)
+        if not _is_torch_tensor(out) or out.dim() != 3 or tuple(out.shape) != (3, d, n):
+            raise ValueError(f"out must be a float32 tensor of shape (3, {d}, {n}) on {dev}")
+        _, jac_ld = self._log_rows(out.permute(1, 0, 2), "out", 3, torch.float32)
+        pos = torch.empty((3, n), dtype=torch.float32, device=dev) if position else None
+        self._torch_call(self._lib.mt_jacobian, ang.data_ptr() if ang is not None else None, ang_ld, out.data_ptr(), jac_ld,
+                         pos.data_ptr() if position else None, n, commits=False)
+        del ang
+        return (out, pos) if position else out
+
+    def ik(self, targets=None, start=None, *, iters=16, damping=2.0, max_step=30.0, tol=0.0, wrap=True, stage=False,
+           residual=True, steps=False, index=None, angles=True):
+        """Which joint angles put the pickup frame on that point?  `iters` damped-least-squares iterations per env in ONE
+        launch (mt_ik): e = x - p(q); dq = degrees(J^T (J J^T + damping^2 I)^-1 e), scaled so that no joint moves more than
+        `max_step` degrees per iteration; q += dq.  targets: (3, N) or (N, 3) points; None = each env's nearest alive target
+        (squared Euclidean distance from the pickup frame at the start pose, lowest index on a tie).  start: (D, N) or
+        (N, D) degrees; None = the resident pose.  Float32 device tensors of shape (rows, N) are read in place, [..., :N]
+        views of wider buffers included.  tol > 0: an env whose box residual max |e_a| is <= tol before an iteration stops
+        there -- bit for bit the angles of a call with that many iterations.  wrap=True maps the angles into [-180, 180)
+        (action_sample's domain); wrap=False keeps them continuous from the start pose, the short route for step().
+        stage=True also writes the angles to the action buffer: ik(stage=True) then step() is a scripted reach controller.
+        Returns a dict of device tensors: `angles` (D, N) float32, `residual` (N,) float32 -- the box residual at the
+        angles returned -- `steps` (N,) int32 and, in nearest mode (index=None means "then"), `index` (N,) int32, -1 for an
+        env without an alive target (held at its start pose, residual 0).  A non-finite target or an unusable start angle
+        holds that env too, with residual NaN.  Each of angles / residual / steps / index may be False, True or a tensor
+        to write into (`angles`: a [..., :N] view of a wider buffer included).  Stream behaviour as rollout_actions."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        n, d = self.n_envs, self.dof
+        iters = int(iters)
+        if not 1 <= iters <= L.IK_MAX_ITERS:
+            raise ValueError(f"iters must be 1..{L.IK_MAX_ITERS}, got {iters}")
+        damping, max_step, tol = (float(np.float32(v)) for v in (damping, max_step, tol))
+        if not (np.isfinite(damping) and damping > 0):
+            raise ValueError(f"damping must be finite and > 0, got {damping!r}")
+        if not (np.isfinite(max_step) and max_step > 0):
+            raise ValueError(f"max_step must be finite and > 0, got {max_step!r}")
+        if not (np.isfinite(tol) and tol >= 0):
+            raise ValueError(f"tol must be finite and >= 0, got {tol!r}")
+        nearest = targets is None
+        index_given = _is_torch_tensor(index)
+        if not nearest and (index_given or index):
+            raise ValueError("index is the nearest-target mode's output: targets must be None")
+        index = nearest if index is None else index
+        arg = L.MtIk()
+        arg.struct_size = C.sizeof(L.MtIk)
+        arg.iters, arg.damping, arg.max_step_deg, arg.tol = iters, damping, max_step, tol
+        arg.flags = (L.IK_STAGE if stage else 0) | (L.IK_WRAP if wrap else 0)
+        tgt, sta = None, None
+        if not nearest:
+            tgt, arg.target_ld = self._ik_rows(targets, "targets", 3)
+            arg.target = tgt.data_ptr()
+        if start is not None:
+            sta, arg.start_ld = self._ik_rows(start, "start", d)
+            arg.start = sta.data_ptr()
+        res = {}
+        if _is_torch_tensor(angles) or angles:
+            res["angles"] = angles if _is_torch_tensor(angles) else torch.empty((d, n), dtype=torch.float32, device=dev)
+            rows, arg.angles_ld = self._log_rows(res["angles"], "angles", None, torch.float32)
+            if rows != d:
+                raise ValueError(f"angles must have D = {d} rows")
+            arg.angles_out = res["angles"].data_ptr()
+        for name, want, field, dtype in (("residual", residual, "residual_out", torch.float32),
+                                         ("steps", steps, "iters_out", torch.int32), ("index", index, "index_out", torch.int32)):
+            if _is_torch_tensor(want) or want:
+                res[name] = self._ik_vector(want, name, dtype) if _is_torch_tensor(want) else torch.empty(n, dtype=dtype, device=dev)
+                setattr(arg, field, res[name].data_ptr())
+        if not res and not stage:
+            raise ValueError("nothing to compute: no output asked for and stage=False")
+        arg.reserved = 0
+        self._torch_call(self._lib.mt_ik, C.byref(arg), commits=bool(stage))
+        del tgt, sta
+        return res
+
     def observe(self):
         """Environment.get_observations (manytor.py:141-153); result in field OBS."""
         self._call(self._lib.mt_observe)
