@@ -14,10 +14,18 @@ The two kinds of appearance are shuffled on their own and dealt out in runs of B
 stretch in which envs finish, so the re-arming ops have somebody to re-arm and dead targets' codes get zeroed.
 
 Step indices never restart: every sampled call of a sequence takes the index after the last one, whatever ran between.
+
+Three ops take no argument of Data's: jacobian, ik and ik(stage)+step work on whatever the sequence left resident -- the
+pose, and in nearest mode the targets and the alive mask -- so directly behind a reset_random they read the rows a deferred
+reset has yet to write, and in a run of plain appearances rows whose targets were picked, zeroed by observe and re-armed.
+ik(stage)+step is a reach controller's env-step: its angles are fractional, written to the action buffer by a kernel, and
+the sampled steps behind it are the first to start from them.
 """
 import collections
 
 import numpy as np
+
+import ik_ref
 
 SEED = 0x5EC5
 K = 7
@@ -35,6 +43,10 @@ MAX_STEPS = 40
 HEAD_STEPS = 3
 SAVE_AHEAD = 3      # set_state restores the get_state() taken this many ops earlier
 BLOCK = 12          # appearances without a reset in front come in runs of this many, then as many with one
+IK_ITERS = 4        # ik: no early stop, every env with a target makes all of them
+REACH_ITERS = 6     # ik(stage)+step: with the early stop at REACH_TOL, so lanes of a wave diverge and whole waves leave the loop
+REACH_TOL = 1.0
+REACH_FLOOR = 0.05  # ik(stage)+step is not vacuous: at least this share of the envs has a target to reach for and moves
 
 # name -> env-steps the op makes
 MOVING = collections.OrderedDict([
@@ -45,13 +57,14 @@ MOVING = collections.OrderedDict([
     ("shoot(commit=H)", H), ("cem(commit=H)", H), ("mppi(commit=H)", H),
     ("rollout_policy", T_TAPE), ("rollout_policy(auto_reset=True)", T_TAPE),
     ("set(F_GOALS)", 0), ("set(F_POINTS)", 0), ("set(F_ALIVE)", 0), ("set_state", 0),
+    ("ik(stage)+step", 1),
 ])
 POPULATION = collections.OrderedDict([("rollout_population", T_TAPE), ("es", T_TAPE)])
 NOTHING = ("rollout_actions(dry_run=True)", "shoot(commit=0)", "cem(commit=0)", "mppi(commit=0)", "sample_plans", "sample_population",
            "policy_eval", "policy_grad", "value_grad", "gae", "reward_to_go", "observe", "check_done", "bad_action_count", "get",
-           "sync", "return_stats", "gather_begin+gather_wait", "gather_returns", "lap_begin+lap_end", "dispatch")
+           "sync", "return_stats", "gather_begin+gather_wait", "gather_returns", "lap_begin+lap_end", "dispatch", "jacobian", "ik")
 # the calls MT_ENTER_KEEP serves (they keep the host's record of MT_F_GOALS): the sampled steps behind them still re-derive
-KEEPERS = ("sync", "get", "observe", "check_done", "bad_action_count", "lap_begin+lap_end")
+KEEPERS = ("sync", "get", "observe", "check_done", "bad_action_count", "lap_begin+lap_end", "jacobian", "ik")
 LOG_MAKERS = ("rollout_policy", "rollout_policy(auto_reset=True)")
 LOG_USERS = ("policy_eval", "policy_grad", "value_grad", "gae", "reward_to_go")
 FULL_RESETS = ("reset(points)",)
@@ -410,6 +423,13 @@ class Runner:
             e.lap_end()
         elif op == "dispatch":
             e.dispatch()
+        elif op == "jacobian":
+            out = dict(zip(("jacobian", "position"), e.jacobian(position=True)))
+        elif op == "ik":
+            out = e.ik(iters=IK_ITERS, tol=0.0, steps=True)
+        elif op == "ik(stage)+step":
+            out = e.ik(stage=True, iters=REACH_ITERS, tol=REACH_TOL, steps=True)
+            e.step()
         else:
             raise KeyError(op)
         return dict(out or {})
@@ -520,6 +540,15 @@ class OracleFollower:
             self.last[key][idx] = v
         self.done_state[idx] = done.astype(np.uint8)
 
+    def reach(self, iters, tol):
+        """What ik(iters=, tol=) in nearest mode from the resident pose returns, by ik_ref on the oracle's own state:
+        (angles (m, D), residual, steps, index), wrapped into [-180, 180); an env without an alive target is held."""
+        o = self.ora
+        index, _ = ik_ref.nearest(o.points, o.alives, o.goals, o.table, o.ee_frame)
+        x = o.points[np.arange(o.n), np.maximum(index, 0)]
+        angles, residual, steps = ik_ref.ik(x, o.goals, o.table, o.ee_frame, iters=iters, tol=tol, wrap=True, hold=index < 0)
+        return angles, residual, steps, index
+
     # ---- the sequence ----
     def item(self, it):
         if it[0] == "reset_random":
@@ -572,7 +601,7 @@ class OracleFollower:
             for q in range(T_TAPE):
                 self.step(tape[q][s], auto_reset="True" in op)
         elif op in ("shoot(commit=H)", "cem(commit=H)", "mppi(commit=H)", "rollout_policy", "rollout_policy(auto_reset=True)",
-                    "rollout_population"):
+                    "rollout_population", "ik(stage)+step"):   # (an env ik held is handed its own pose: it stays where it is)
             for a in committed(op):
                 self.step(a, auto_reset="True" in op)
         elif op == "set(F_GOALS)":

@@ -25,6 +25,14 @@ POS_TOL = 4.0 * POS_MEASURED
 # over the same arms, measured on an MI355X.
 STEP_MEASURED = 8.702e-04   # degrees (the reference arm through the runtime table, n = 200)
 STEP_TOL = 4.0 * STEP_MEASURED
+# max |angles - ik_ref.ik| in degrees, modulo 360, after FOUR iterations without early stop (damping 2, max_step 30, wrapped)
+# from the fractional mid-episode poses of tests/test_gpu_call_sequences.py's oracle leg towards each env's nearest alive
+# target: the reference arm, every regime of that test, over the unguarded sampled envs, measured on an MI355X.
+# Far above four times STEP_MEASURED because the iteration itself amplifies: this fp64 restatement, run twice from the zero
+# pose with the targets moved by 1e-5 (one fp32 rounding of the chain), differs from itself by up to 2.7e-2 degrees after
+# three iterations (median 2.5e-5); the few envs near a singular pose set the maximum.
+SEQ_STEP_MEASURED = 3.683e-02   # degrees (multi / per_step / chains / pop_*: the first ik of the sequence, about 3 000 envs)
+SEQ_STEP_TOL = 4.0 * SEQ_STEP_MEASURED
 # for orientation: a plain fp32 numpy restatement of the iteration differs from fp64 by at most this on 4 096 such cases
 STEP_REF32_MEASURED = 1.8e-3
 RESIDUAL_TOL = 1e-3         # residual_out against the fp64 residual of the RETURNED angles

@@ -32,12 +32,15 @@ Which leg holds which op:
           shoot(commit=H) (the plan rows best[i]), cem(commit=H) and mppi(commit=H) (their `chosen` output names the committed
           angles), rollout_policy (both; its action log: the dynamics under a policy, the MLP is held by test_gpu_policy.py),
           rollout_population (its action log), set(F_GOALS / F_POINTS / F_ALIVE), set_state, observe and check_done (the
-          oracle repeats them: get_observations / is_done)
+          oracle repeats them: get_observations / is_done), ik(stage)+step (its `angles` output names the staged angles; an
+          env it held is handed its own pose)
   twin    es: no output of the call names the actions it committed, so it is left out of the oracle leg's sequence
   twin, and the handle against itself (fields before == fields after the op)
           rollout_actions(dry_run=True), shoot / cem / mppi(commit=0), sample_plans, sample_population, policy_eval,
           policy_grad, value_grad, gae, reward_to_go, bad_action_count, get, sync, return_stats, gather_begin+gather_wait,
           gather_returns, lap_begin+lap_end, dispatch; the oracle leg runs them too, as calls between its steps.
+  twin, the handle against itself, and tests/ik_ref.py in fp64 on the oracle's own pose, targets and alive mask
+          jacobian, ik -- and the ik half of ik(stage)+step, ahead of its step (compare_ik_with_reference)
 Two of the "change nothing" ops are recomputations, not no-ops, and are held as such: observe rewrites MT_F_OBS from the
 state AFTER the pickups (a target picked in the last step reads 0 where the step's observation, taken before the pickup,
 had a distance) and zeroes the coordinates of dead targets (manytor.py:148); check_done repeats the pickup test, which right
@@ -51,6 +54,7 @@ import numpy as np
 import pytest
 
 import call_sequences as cs
+import ik_ref
 from parity_util import DIST_TOL, GUARD, POS_TOL, assert_obs_close
 
 pytestmark = pytest.mark.gpu
@@ -290,6 +294,8 @@ def test_sequence_against_the_twin(m, monkeypatch, regime, shuffle):
             c0 = rederived(eng)
             out = ra.op(g)
             assert_same_outputs(out, rb.op(g), what)
+            if g.op == "ik(stage)+step":   # not on held envs only
+                assert float(((out["index"] >= 0) & (out["steps"] > 0)).float().mean()) >= cs.REACH_FLOOR, what
             if nothing:
                 after = ra.snapshot()
                 if g.with_reset:
@@ -328,6 +334,8 @@ def committed_actions(op, out, data, sample, idx):
         best = out["best"].index_select(0, idx).cpu().numpy()
         plans = data.plans[:, :cs.H][..., sample]                       # (C, H, D, m)
         return plans[best, :, :, np.arange(len(sample))].transpose(1, 0, 2)
+    if op == "ik(stage)+step":
+        return out["angles"].index_select(1, idx).cpu().numpy().T[None]
     key = "chosen" if op in ("cem(commit=H)", "mppi(commit=H)") else "actions"
     return out[key].index_select(2, idx).cpu().numpy().transpose(0, 2, 1)
 
@@ -365,6 +373,56 @@ def compare_with_oracle(runner, idx, fo, what, out=None, only=None):
             np.testing.assert_array_equal(out["returns"].index_select(0, idx).cpu().numpy()[ok], total[ok].astype(np.float32), err_msg=what)
 
 
+def compare_jacobian_with_reference(op, out, idx, fo, what):
+    """jacobian(position=True) of the resident pose against ik_ref on the oracle's pose (fp32 actions: the same numbers)."""
+    ok = ~fo.guarded
+    J_ref, p_ref = ik_ref.jacobian(fo.ora.goals, ik_ref.REF_TABLE)
+    J = out["jacobian"].index_select(2, idx).cpu().numpy().transpose(2, 0, 1)        # (m, 3, D)
+    p = out["position"].index_select(1, idx).cpu().numpy().T
+    worst_j, worst_p = np.abs(J - J_ref)[ok].max(), np.abs(p - p_ref)[ok].max()
+    print(f"{what}: jacobian off by {worst_j:.3e} per degree, position by {worst_p:.3e}")
+    assert worst_j <= ik_ref.JAC_TOL and worst_p <= ik_ref.POS_TOL, (what, worst_j, worst_p)
+
+
+def compare_ik_with_reference(op, out, idx, fo, what):
+    """ik in nearest mode from the resident pose against ik_ref on the oracle's own pose, targets and alive mask, over the
+    unguarded envs: for those the three rows hold the oracle's numbers exactly (poses are committed fp32 actions, targets are
+    fp32 draws).  `ik`: 4 iterations, no early stop; the ik of ik(stage)+step: up to 6, stopping at a box residual of 1."""
+    o = fo.ora
+    staged = op == "ik(stage)+step"
+    ok = ~fo.guarded
+    q0 = o.goals
+    angles = out["angles"].index_select(1, idx).cpu().numpy().T                      # (m, D)
+    residual, steps, index = (out[key].index_select(0, idx).cpu().numpy() for key in ("residual", "steps", "index"))
+    # the target: none exactly where the oracle has none alive, else an alive one within 1e-3 of the nearest (fp64 distances)
+    none = ~o.alives.any(axis=1)
+    np.testing.assert_array_equal((index == -1)[ok], none[ok], err_msg=what)
+    live, held = np.flatnonzero(ok & ~none), ok & none
+    assert (index[live] >= 0).all() and (index[live] < cs.K).all() and o.alives[live, index[live]].all(), what
+    _, d2 = ik_ref.nearest(o.points, o.alives, q0, ik_ref.REF_TABLE)
+    assert (np.sqrt(d2[live, index[live]]) <= np.sqrt(d2[live].min(axis=1)) + 1e-3).all(), what
+    # held envs: the start pose bit for bit
+    np.testing.assert_array_equal(bits(angles[held]), bits(q0[held].astype(np.float32)), err_msg=what)
+    assert (residual[held] == 0).all() and (steps[held] == 0).all(), what
+    # the residual reported is the box residual of the angles returned
+    x = o.points[live, index[live]]
+    box = ik_ref.box(x - ik_ref.position(angles[live].astype(np.float64), ik_ref.REF_TABLE))
+    assert np.abs(residual[live] - box).max(initial=0.0) <= ik_ref.RESIDUAL_TOL, what
+    if staged:
+        assert (steps[live] <= cs.REACH_ITERS).all(), what
+        early = steps[live] < cs.REACH_ITERS
+        assert (residual[live][early] <= cs.REACH_TOL + ik_ref.RESIDUAL_TOL).all(), what
+        share = ((index >= 0) & (steps > 0)).mean()                                  # not on held envs only
+        print(f"{what}: {100 * share:.1f} % of the sample reach for a target, {100 * early.mean():.1f} % of those stopped early")
+        assert share >= cs.REACH_FLOOR, (what, share)
+    else:
+        assert (steps[live] == cs.IK_ITERS).all() and len(live) > 0, what
+        ref = ik_ref.ik(x, q0[live], ik_ref.REF_TABLE, iters=cs.IK_ITERS, wrap=True)[0]
+        worst = np.abs(ik_ref.wrap180(angles[live] - ref)).max()
+        print(f"{what}: angles off by {worst:.3e} degrees after {cs.IK_ITERS} iterations ({len(live)} envs)")
+        assert worst <= ik_ref.SEQ_STEP_TOL, (what, worst)
+
+
 @pytest.mark.parametrize("regime", list(REGIMES))
 def test_sequence_in_lockstep_with_the_fp64_oracle(m, monkeypatch, regime):
     import torch
@@ -388,6 +446,8 @@ def test_sequence_in_lockstep_with_the_fp64_oracle(m, monkeypatch, regime):
                 ra.item(it)
                 fo.item(it)
             out = ra.op(g)
+            if g.op in ("jacobian", "ik", "ik(stage)+step"):     # ahead of the oracle's own step: on the state the call read
+                (compare_jacobian_with_reference if g.op == "jacobian" else compare_ik_with_reference)(g.op, out, idx, fo, what)
             fo.op(g, lambda op: committed_actions(op, out, data, sample, idx))
             if cs.op_steps(g.op):
                 compare_with_oracle(ra, idx, fo, what, out, only=fo.single if g.op == "env_step" else None)

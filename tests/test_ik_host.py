@@ -205,3 +205,4 @@ def test_tolerance_constants_are_consistent():
     assert ik_ref.JAC_MEASURED > 0 and ik_ref.POS_MEASURED > 0 and ik_ref.STEP_MEASURED > 0
     assert ik_ref.JAC_TOL == 4.0 * ik_ref.JAC_MEASURED and ik_ref.POS_TOL == 4.0 * ik_ref.POS_MEASURED
     assert ik_ref.STEP_TOL == 4.0 * ik_ref.STEP_MEASURED
+    assert ik_ref.SEQ_STEP_MEASURED > 0 and ik_ref.SEQ_STEP_TOL == 4.0 * ik_ref.SEQ_STEP_MEASURED
