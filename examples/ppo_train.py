@@ -7,8 +7,10 @@ transposed copy of the logs: every pass over the samples is one engine call on t
      bootstrap V(x_T) from observe() and the resident observation rows, read in place as a one-step block
   3. gae(reward, done, V, last_value=V(x_T), mask_after_done=True, weights=True): advantages, value targets, and the
      weights that take the steps behind an env's episode end out of both gradients
-  4. a few epochs of: policy_eval for the new log pi; ratio, clip mask and coef as four elementwise torch lines on (T, N);
-     policy_grad(coef) and value_grad(returns, weights); two steps of fixed length
+  4. a few epochs of: policy_grad(adv, old_logp=, clip=, weights=) -- the new log pi, the ratio, the clip decision and the
+     gradient in ONE pass over the logs, with the clipped and used counts beside it -- and value_grad(returns, weights); two
+     steps of fixed length.  --parts runs the same epoch as the parts that call replaces: policy_eval for the new log pi,
+     ratio, clip mask and coef as four elementwise torch lines on (T, N), policy_grad(coef): a second forward pass.
 
 No learning curve is promised: this is the shape of the loop, with the plainest step rule that does not diverge.
 
@@ -37,6 +39,7 @@ ap.add_argument("--clip", type=float, default=0.2)
 ap.add_argument("--lr", type=float, default=0.0003, help="length of the policy's step: theta += lr * grad / |grad|")
 ap.add_argument("--value-lr", type=float, default=0.02, help="length of the critic's step")
 ap.add_argument("--seed", type=int, default=1)
+ap.add_argument("--parts", action="store_true", help="policy_eval + four torch lines + policy_grad instead of the one fused call")
 args = ap.parse_args()
 
 eng = m.StepEngine(args.envs, args.targets)
@@ -70,12 +73,17 @@ for it in range(args.iterations):
                   weights=True)
     adv, returns, weights = est["advantages"], est["returns"], est["weights"]
     for epoch in range(args.epochs):
-        new = eng.policy_eval(theta, obs, actions=actions, mean=False, **pi)["logp"]
-        ratio = torch.exp(new - old)
-        clipped = ((ratio > 1 + args.clip) & (adv > 0)) | ((ratio < 1 - args.clip) & (adv < 0))
-        coef = torch.where(clipped, torch.zeros_like(adv), ratio * adv)      # d/dtheta of min(ratio A, clip(ratio) A)
-        clip_fraction = clipped.float().sum() / weights.sum()
-        eng.policy_grad(theta, obs, actions, coef, scale=1.0 / args.envs, grad_out=grad, **pi)
+        if args.parts:
+            new = eng.policy_eval(theta, obs, actions=actions, mean=False, **pi)["logp"]
+            ratio = torch.exp(new - old)
+            clipped = ((ratio > 1 + args.clip) & (adv > 0)) | ((ratio < 1 - args.clip) & (adv < 0))
+            coef = torch.where(clipped, torch.zeros_like(adv), ratio * adv)      # d/dtheta of min(ratio A, clip(ratio) A)
+            clip_fraction = clipped.float().sum() / weights.sum()
+            eng.policy_grad(theta, obs, actions, coef, scale=1.0 / args.envs, grad_out=grad, **pi)
+        else:
+            res = eng.policy_grad(theta, obs, actions, adv, old_logp=old, clip=args.clip, weights=weights, scale=1.0 / args.envs,
+                                  grad_out=grad, **pi)
+            clip_fraction = res["clipped"] / res["used"].clamp_min(1)
         _, vloss = eng.value_grad(phi, obs, returns, weights, widths=widths, scale=1.0 / args.envs, grad_out=vgrad, loss=True)
         theta += (args.lr / grad.norm().clamp_min(1e-20)) * grad
         phi += (args.value_lr / vgrad.norm().clamp_min(1e-20)) * vgrad

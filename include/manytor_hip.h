@@ -41,7 +41,7 @@ extern "C" {
 #define MT_API
 #endif
 
-#define MT_VERSION 480       /* major*10000 + minor*100 + patch */
+#define MT_VERSION 490       /* major*10000 + minor*100 + patch */
 #define MT_MAX_DOF 8
 #define MT_MAX_TARGETS 32
 #define MT_MAX_RETURN_RING 64
@@ -756,6 +756,82 @@ MT_API int mt_value_grad(mt_handle h, const struct mt_value_grad* p);
 /* Bytes of workspace mt_value_grad needs on this handle for a value head of that shape and n_steps (0 for n_steps == 0,
  * and for arguments mt_value_grad would refuse). */
 MT_API size_t mt_value_grad_workspace(mt_handle h, int n_layers, const int32_t width[2], uint32_t flags, int n_steps);
+
+/* PPO's clipped surrogate gradient in one pass over the logs: mt_policy_grad with the coefficient of every sample formed
+ * in the kernel from its NEW log-probability (which the kernel holds anyway), the logged old one and the advantage --
+ * instead of mt_policy_eval, four elementwise passes over (T, n_envs) and mt_policy_grad's second forward pass -- plus
+ * what a PPO loop logs and what a learned exploration width needs.
+ *
+ * Samples, x, a, mu and the layers are mt_policy_grad's.  With lo = fl32(1 - (double)clip), hi = fl32(1 + (double)clip)
+ * formed once on the host, per sample s = (t, i), all in fp32:
+ *   A       = weight[t, i] * adv[t, i]                   (A = adv[t, i] without weight)
+ *   skipped   when A == 0 or any a_j is unusable (the rule of every tape): x, a and old_logp of such a sample are never
+ *             read into the arithmetic, NaN among them included.  Every other sample is USED.
+ *   new     = mt_policy_eval's logp, bit for bit           (-0.5f * lp, lp by mt_policy_grad's fmaf chain)
+ *   x       = min(max((new - old_logp[t, i]) + log_ratio_shift, -MT_PPO_MAX_LOG_RATIO), MT_PPO_MAX_LOG_RATIO)
+ *   ratio   = exp(x)                                       (the hardware's exp2 of the rounded x * log2(e): about
+ *                                                           1.2e-7 + 6e-8 |x| relative, the same bits for the same x)
+ *   clipped = clip > 0 && ((A > 0 && ratio > hi) || (A < 0 && ratio < lo))
+ *   c       = clipped ? 0 : ratio * A
+ *   obj     = clipped ? (A > 0 ? hi : lo) * A : c          = min(ratio A, clamp(ratio, lo, hi) A)
+ * and
+ *   grad_out          = scale * sum_s c_s d logp_s / d theta: EXACTLY mt_policy_grad's grad_out for coef = c (the same
+ *                       deltas, images, accumulation order, grid and reduction: bit for bit on the same handle)
+ *   loss_out          = scale * sum_s obj_s                 (the surrogate objective; theta += lr * grad ascends it)
+ *   kl_out            = scale * sum over used s of ((ratio - 1) - x)       (the k3 estimator of KL(old || new))
+ *   sigma_grad_out[j] = scale * sum_s c_s fmaf(e_j, d_j, -1),  e_j = a_j - mu_j, d_j = e_j * inv_var_j: d / d log sigma_j
+ *                       of the full Gaussian log-density (its normaliser included)
+ *   count_out         = {used, clipped}: int64 counts, exact at any size
+ *   ratio_out[t, i], coef_out[t, i] = ratio, c; a skipped sample gets 0 in both.
+ * clip == 0 never clips: c = ratio * A, the importance-weighted policy gradient.  log_ratio_shift is
+ * sum_j log(sigma_old_j / sigma_j) when sigma changed since old_logp was taken (logp drops the normaliser), else 0.
+ * adv, old_logp and weight are device memory and cannot be screened: they are expected to be finite; a NaN or an infinity
+ * among the USED samples leaves the sums unspecified.
+ * Contract.  mt_policy_grad's: two launches on the handle's stream (one when n_steps == 0, which writes zeros to every
+ * output given), no allocation, no host wait, legal under stream capture, no floating-point atomics -- the same arguments
+ * give the same bits; the bits do not depend on the ld's.  Everything the host can see is screened: clip must be 0 or in
+ * (0, 1), log_ratio_shift and scale finite, every ld >= n_envs, count_out 8-byte aligned, and no output may overlap the
+ * weights, an input or another output (the workspace counts as an output).  The workspace holds
+ * blocks x (P + 1 + MT_PPO_EXTRA_WORDS) words -- per block: the gradient, the objective, the KL sum, MT_MAX_DOF sigma sums
+ * and the two counts -- mt_ppo_grad_workspace() bytes; the second launch adds the rows in ascending block order (the
+ * counts as integers) and applies scale once.  Columns [n_envs, ld) of no row are read or written. */
+#define MT_PPO_MAX_LOG_RATIO 20.0f
+#define MT_PPO_EXTRA_WORDS (MT_MAX_DOF + 3)
+struct mt_ppo_grad {       /* as with mt_cem, the type is always written `struct mt_ppo_grad` */
+  int32_t struct_size;     /* = sizeof(struct mt_ppo_grad), checked */
+  int32_t n_steps;         /* T, 0..65535 */
+  int32_t n_layers;        /* L, as mt_policy */
+  int32_t width[2];
+  int32_t hidden_act;
+  int32_t out_act;
+  const float* weight[3];  /* DEVICE f32, as mt_policy: the network's matrices */
+  const float* bias[3];
+  float out_scale;         /* finite */
+  float sigma[MT_MAX_DOF]; /* per joint, degrees: finite, > 0 for j < D (entries behind D: finite, >= 0, not read) */
+  uint32_t flags;          /* MT_POLICY_SEE_POSE only: it fixes IN */
+  const float* obs;      int64_t obs_ld;    /* DEVICE (T, IN, obs_ld) */
+  const float* action;   int64_t act_ld;    /* DEVICE (T, D, act_ld) */
+  const float* adv;      int64_t adv_ld;    /* DEVICE (T, adv_ld) f32: the advantages */
+  const float* old_logp; int64_t old_ld;    /* DEVICE (T, old_ld) f32: mt_policy_eval's logp when the actions were taken */
+  const float* sample_weight; int64_t weight_ld; /* DEVICE (T, weight_ld) f32 or NULL (= 1), e.g. mt_gae's weight_out */
+  float clip;              /* 0 (no clipping) or in (0, 1) */
+  float log_ratio_shift;   /* finite */
+  float scale;             /* finite; applied once, at the final conversion */
+  float* grad_out;         /* DEVICE f32 (P,): always written */
+  float* loss_out;         /* DEVICE f32 (1,) or NULL */
+  float* ratio_out;      int64_t ratio_ld;  /* DEVICE (T, ratio_ld) or NULL */
+  float* coef_out;       int64_t coef_ld;   /* DEVICE (T, coef_ld) or NULL */
+  float* sigma_grad_out;   /* DEVICE f32 (D,) or NULL */
+  float* kl_out;           /* DEVICE f32 (1,) or NULL */
+  int64_t* count_out;      /* DEVICE int64 (2,) or NULL: used, clipped */
+  void* workspace;         /* DEVICE, 4-byte aligned; may be NULL when mt_ppo_grad_workspace() is 0 */
+  size_t workspace_bytes;  /* >= mt_ppo_grad_workspace() */
+  uint64_t reserved;       /* must be 0 */
+};
+MT_API int mt_ppo_grad(mt_handle h, const struct mt_ppo_grad* p);
+/* Bytes of workspace mt_ppo_grad needs on this handle for a policy of that shape and n_steps (0 for n_steps == 0, and for
+ * arguments mt_ppo_grad would refuse). */
+MT_API size_t mt_ppo_grad_workspace(mt_handle h, int n_layers, const int32_t width[2], uint32_t flags, int n_steps);
 
 /* Environment.get_observations(), manytor.py:141-153, at the current pose (also
  * zeroes the coordinates of dead targets, :148).  Result in MT_F_OBS. */

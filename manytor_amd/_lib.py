@@ -446,6 +446,52 @@ class MtValueGrad(C.Structure):
 GAE_MASK_AFTER_DONE = 0x1
 
 
+class MtPpoGrad(C.Structure):
+    """struct mt_ppo_grad of include/manytor_hip.h: the argument block of mt_ppo_grad."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_steps", C.c_int32),
+        ("n_layers", C.c_int32),
+        ("width", C.c_int32 * 2),
+        ("hidden_act", C.c_int32),
+        ("out_act", C.c_int32),
+        ("weight", C.c_void_p * 3),
+        ("bias", C.c_void_p * 3),
+        ("out_scale", C.c_float),
+        ("sigma", C.c_float * MT_MAX_DOF),
+        ("flags", C.c_uint32),
+        ("obs", C.c_void_p),
+        ("obs_ld", C.c_int64),
+        ("action", C.c_void_p),
+        ("act_ld", C.c_int64),
+        ("adv", C.c_void_p),
+        ("adv_ld", C.c_int64),
+        ("old_logp", C.c_void_p),
+        ("old_ld", C.c_int64),
+        ("sample_weight", C.c_void_p),
+        ("weight_ld", C.c_int64),
+        ("clip", C.c_float),
+        ("log_ratio_shift", C.c_float),
+        ("scale", C.c_float),
+        ("grad_out", C.c_void_p),
+        ("loss_out", C.c_void_p),
+        ("ratio_out", C.c_void_p),
+        ("ratio_ld", C.c_int64),
+        ("coef_out", C.c_void_p),
+        ("coef_ld", C.c_int64),
+        ("sigma_grad_out", C.c_void_p),
+        ("kl_out", C.c_void_p),
+        ("count_out", C.c_void_p),
+        ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_size_t),
+        ("reserved", C.c_uint64),
+    ]
+
+
+PPO_MAX_LOG_RATIO = 20.0
+PPO_EXTRA_WORDS = MT_MAX_DOF + 3
+
+
 class MtIk(C.Structure):
     """struct mt_ik of include/manytor_hip.h: the argument block of mt_ik."""
     _fields_ = [
@@ -516,6 +562,8 @@ PROTOTYPES = {
     "mt_gae": (C.c_int, [_HANDLE, C.POINTER(MtGae)]),
     "mt_value_grad": (C.c_int, [_HANDLE, C.POINTER(MtValueGrad)]),
     "mt_value_grad_workspace": (C.c_size_t, [_HANDLE, C.c_int, C.POINTER(C.c_int32), C.c_uint32, C.c_int]),
+    "mt_ppo_grad": (C.c_int, [_HANDLE, C.POINTER(MtPpoGrad)]),
+    "mt_ppo_grad_workspace": (C.c_size_t, [_HANDLE, C.c_int, C.POINTER(C.c_int32), C.c_uint32, C.c_int]),
     "mt_ik": (C.c_int, [_HANDLE, C.POINTER(MtIk)]),
     "mt_jacobian": (C.c_int, [_HANDLE, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "mt_observe": (C.c_int, [_HANDLE]),

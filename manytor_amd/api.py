@@ -361,7 +361,10 @@ class Multienv:
     def policy_gradient(self, layers_or_theta, obs, actions, coef, **kw):
         """scale * sum over the logged samples of coef * d log pi(action | obs) / d theta, as one flat vector in
         flatten_policy's layout (StepEngine.policy_grad, which documents the keywords; StepEngine.reward_to_go makes the
-        usual `coef` from run-time logs).  Nothing of the envs is read or moved."""
+        usual `coef` from run-time logs).  With old_logp= (evaluate_policy's `logp` when the actions were taken) the call is
+        PPO's clipped surrogate in one pass: `coef` holds the advantages, clip=, weights=, sigma_old=, ratio=, coef_out= and
+        sigma_grad= are read, and a dict comes back -- `grad`, `loss`, `kl`, `used`, `clipped` and the outputs asked for.
+        Nothing of the envs is read or moved."""
         return self._engine.policy_grad(layers_or_theta, obs, actions, coef, **kw)
 
     def evaluate_policy(self, layers_or_theta, obs, **kw):

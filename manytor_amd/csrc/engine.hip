@@ -2911,6 +2911,133 @@ int mt_value_grad(mt_handle h, const struct mt_value_grad* p) {
   return policy_grad_call(h, c, "mt_value_grad");
 }
 
+// mt_ppo_grad: mt_policy_grad's screens, grid and first-pass kernel (in its PPO mode), rows of kPpoExtras more words
+static size_t ppo_grad_row_bytes(const PolicyLayout& s) { return (size_t)(s.P + 1 + kPpoExtras) * sizeof(float); }
+size_t mt_ppo_grad_workspace(mt_handle h, int n_layers, const int32_t width[2], uint32_t flags, int n_steps) {
+  PolicyLayout s;
+  const int32_t none[2] = {0, 0};
+  if (!h || n_steps <= 0 || n_steps > 65535 || !policy_layout(h, n_layers, width ? width : none, flags, &s)) return 0;
+  return (size_t)policy_grad_blocks(h, n_steps) * ppo_grad_row_bytes(s);
+}
+int mt_ppo_grad(mt_handle h, const struct mt_ppo_grad* p) {
+  MT_REQUIRE(h, p != nullptr, "ppo_grad is NULL");  // (the struct first: its size is checked with or without a handle)
+  MT_REQUIRE(h, p->struct_size == (int32_t)sizeof(struct mt_ppo_grad), "mt_ppo_grad.struct_size does not match this library");
+  const std::string w = "mt_ppo_grad";
+  const PolicyNet net = MT_POLICY_NET(p);
+  // what needs no handle: the scalars
+  int rc = policy_net_screen(h, net, w);
+  if (rc) return rc;
+  MT_REQUIRE(h, first_unusable(&p->scale, 1, kMaxFiniteBits) < 0, w + ".scale must be finite");
+  MT_REQUIRE(h, first_unusable(&p->clip, 1, kMaxFiniteBits) < 0 && (p->clip == 0.f || (p->clip > 0.f && p->clip < 1.f)),
+             w + ".clip must be 0 (no clipping) or in (0, 1)");
+  MT_REQUIRE(h, first_unusable(&p->log_ratio_shift, 1, kMaxFiniteBits) < 0, w + ".log_ratio_shift must be finite");
+  if ((rc = policy_sigma_screen(h, p->sigma, 1, w))) return rc;
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  const int L = p->n_layers, T = p->n_steps, D = h->D;
+  for (int j = 0; j < D; ++j) MT_REQUIRE(h, p->sigma[j] > 0.f, w + ".sigma[" + std::to_string(j) + "] must be finite and > 0");
+  PolicyLayout s;
+  MT_REQUIRE(h, policy_layout(h, L, p->width, p->flags, &s), w + ": not a policy shape");
+  const int64_t n = h->n, P = s.P;
+  const int IN = s.n_in[0];
+  MT_REQUIRE(h, p->grad_out != nullptr, w + ".grad_out is NULL");
+  MT_REQUIRE(h, ((uintptr_t)p->count_out & 7u) == 0, w + ".count_out is not 8-byte aligned");
+  const size_t need = T ? (size_t)policy_grad_blocks(h, T) * ppo_grad_row_bytes(s) : 0;
+  if (T) {
+    for (int l = 0; l < L; ++l)
+      MT_REQUIRE(h, p->weight[l] != nullptr && p->bias[l] != nullptr, w + ".weight / bias [" + std::to_string(l) + "] is NULL");
+    MT_REQUIRE(h, p->obs != nullptr && p->action != nullptr && p->adv != nullptr && p->old_logp != nullptr,
+               w + ".obs / action / adv / old_logp is NULL");
+    MT_REQUIRE(h, p->obs_ld >= n, w + ".obs_ld is smaller than n_envs");
+    MT_REQUIRE(h, p->act_ld >= n, w + ".act_ld is smaller than n_envs");
+    MT_REQUIRE(h, p->adv_ld >= n, w + ".adv_ld is smaller than n_envs");
+    MT_REQUIRE(h, p->old_ld >= n, w + ".old_ld is smaller than n_envs");
+    MT_REQUIRE(h, p->sample_weight == nullptr || p->weight_ld >= n, w + ".weight_ld is smaller than n_envs");
+    MT_REQUIRE(h, p->ratio_out == nullptr || p->ratio_ld >= n, w + ".ratio_ld is smaller than n_envs");
+    MT_REQUIRE(h, p->coef_out == nullptr || p->coef_ld >= n, w + ".coef_ld is smaller than n_envs");
+    MT_REQUIRE(h, p->workspace != nullptr && ((uintptr_t)p->workspace & 3u) == 0, w + ".workspace is NULL or not 4-byte aligned");
+    MT_REQUIRE(h, p->workspace_bytes >= need, w + ".workspace_bytes is smaller than " + w + "_workspace() = " + std::to_string(need));
+  }
+  {  // the outputs against the weights, the inputs and each other (what n_steps == 0 leaves unread has no bytes)
+    const auto rows = [&](const void* q, int64_t r, int64_t ld) { return (q && T) ? rows_bytes(r, ld, n) : (size_t)0; };
+    const Span out[8] = {{p->grad_out, (size_t)P * 4, "grad_out"},
+                         {p->loss_out, p->loss_out ? (size_t)4 : 0, "loss_out"},
+                         {p->sigma_grad_out, p->sigma_grad_out ? (size_t)D * 4 : 0, "sigma_grad_out"},
+                         {p->kl_out, p->kl_out ? (size_t)4 : 0, "kl_out"},
+                         {p->count_out, p->count_out ? (size_t)16 : 0, "count_out"},
+                         {p->ratio_out, rows(p->ratio_out, T, p->ratio_ld), "ratio_out"},
+                         {p->coef_out, rows(p->coef_out, T, p->coef_ld), "coef_out"},
+                         {p->workspace, need, "workspace"}};
+    const Span in[5] = {{p->obs, rows(p->obs, (int64_t)T * IN, p->obs_ld), "obs"},
+                        {p->action, rows(p->action, (int64_t)T * D, p->act_ld), "action"},
+                        {p->adv, rows(p->adv, T, p->adv_ld), "adv"},
+                        {p->old_logp, rows(p->old_logp, T, p->old_ld), "old_logp"},
+                        {p->sample_weight, rows(p->sample_weight, T, p->weight_ld), "sample_weight"}};
+    PolicyNet weights = net;
+    if (!T) weights.n_layers = 0;  // (not read, and free to be NULL)
+    if ((rc = policy_overlap_screen(h, weights, s, out, 8, in, 5, w))) return rc;
+  }
+  MT_ENTER(h);
+  PpoGradArgs r{};
+  for (int l = 0; l < L; ++l) {
+    r.w[l] = p->weight[l];
+    r.b[l] = p->bias[l];
+    r.n_in[l] = s.n_in[l];
+    r.n_out[l] = s.n_out[l];
+    r.off[l] = s.off[l];
+  }
+  r.L = L;
+  r.T = T;
+  r.K = h->K;
+  r.D = D;
+  r.hidden_act = p->hidden_act;
+  r.out_act = p->out_act;
+  r.out_scale = p->out_scale;
+  for (int j = 0; j < D; ++j) r.inv_var[j] = (float)(1.0 / ((double)p->sigma[j] * (double)p->sigma[j]));
+  r.see_pose = (p->flags & MT_POLICY_SEE_POSE) ? 1u : 0u;
+  r.obs = p->obs;
+  r.obs_ld = p->obs_ld;
+  r.action = p->action;
+  r.act_ld = p->act_ld;
+  r.coef = p->adv;
+  r.coef_ld = p->adv_ld;
+  r.n = n;
+  r.tiles_per_step = (n + kBlock - 1) / kBlock;
+  r.tiles = (int64_t)T * r.tiles_per_step;
+  r.P = P;
+  r.partials = static_cast<float*>(p->workspace);
+  r.blocks = T ? (int32_t)policy_grad_blocks(h, T) : 0;
+  r.scale = p->scale;
+  r.grad = p->grad_out;
+  r.loss = p->loss_out;
+  r.old_logp = p->old_logp;
+  r.old_ld = p->old_ld;
+  r.weight = p->sample_weight;
+  r.weight_ld = p->weight_ld;
+  r.lo = (float)(1.0 - (double)p->clip);
+  r.hi = (float)(1.0 + (double)p->clip);
+  r.shift = p->log_ratio_shift;
+  r.clipping = p->clip > 0.f ? 1u : 0u;
+  r.ratio = p->ratio_out;
+  r.ratio_ld = p->ratio_ld;
+  r.coef_out = p->coef_out;
+  r.coefo_ld = p->coef_ld;
+  r.sigma_grad = p->sigma_grad_out;
+  r.kl = p->kl_out;
+  r.count = reinterpret_cast<long long*>(p->count_out);
+  if (T) {
+    // the (extent, chunks of x) mt_policy_grad picks
+    if (s.widest <= 32)
+      hipLaunchKernelGGL((policy_grad_kernel<32, 4, 1>), dim3((unsigned)r.blocks), dim3(kBlock), 0, h->stream, r);
+    else if (IN <= 64)
+      hipLaunchKernelGGL((policy_grad_kernel<64, 1, 1>), dim3((unsigned)r.blocks), dim3(kBlock), 0, h->stream, r);
+    else
+      hipLaunchKernelGGL((policy_grad_kernel<64, 2, 1>), dim3((unsigned)r.blocks), dim3(kBlock), 0, h->stream, r);
+    if ((rc = check_launch(h, "policy_grad_kernel"))) return rc;
+  }
+  hipLaunchKernelGGL(ppo_grad_reduce_kernel, grid_for(P + 1 + kPpoExtras), dim3(kBlock), 0, h->stream, r);
+  return check_launch(h, "ppo_grad_reduce_kernel");
+}
+
 int mt_policy_eval(mt_handle h, const struct mt_policy_eval* p) {
   MT_REQUIRE(h, p != nullptr, "policy_eval is NULL");  // (the struct first: its size is checked with or without a handle)
   MT_REQUIRE(h, p->struct_size == (int32_t)sizeof(struct mt_policy_eval), "mt_policy_eval.struct_size does not match this library");

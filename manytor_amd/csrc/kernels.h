@@ -2988,6 +2988,17 @@ __global__ __launch_bounds__(kBlock) void es_update_kernel(const EsArgs r) {
 //             x = 0, a = 0, c = 0: every delta is then +-0, and adds nothing.
 // Each block writes its sums to its row of the (blocks, P + 1) partials (word P: the loss); policy_grad_reduce_kernel adds
 // the rows in ascending block order and applies scale once.
+//
+// policy_grad_kernel<W, NCH0, 1>, the PPO mode (mt_ppo_grad): a compile-time mode, so the two-parameter instantiations are
+// the text they were.  `coef` holds the advantages; the lane carries A = weight * adv where the plain mode carries c, and
+// once the j loop has finished lp it forms x, ratio and the clip decision, c = clipped ? 0 : ratio * A, and only then
+// dl[j] = ((c * d[j]) * out_scale) * slope[j]: the plain mode's expression on the same d and slope, so the deltas -- and
+// everything behind them -- are mt_policy_grad's for coef = c.  (e, d and the slope are formed a second time from y[j], by
+// the same expressions and so with the same bits, rather than kept across the ratio: kept, they are 3 D live registers
+// more and the W = 64 instantiations spill 64 and 132 bytes per lane to scratch; formed twice, none does.)  The lane also keeps the objective (in `loss`) and, in LDS
+// words of its own (ppo_lane_sums), the KL sum, D sigma sums and two counters across its tiles; they are added in thread
+// order behind the tile loop and go to the kPpoExtras words behind word P of the block's row, which
+// ppo_grad_reduce_kernel adds like the others (the two counts as integers).
 // ---------------------------------------------------------------------------
 struct PolicyGradArgs {
   const float* w[3];
@@ -3014,6 +3025,39 @@ struct PolicyGradArgs {
   float* grad;  // [P]
   float* loss;  // [1] or NULL
 };
+// the words behind the loss in a block's row of mt_ppo_grad's partials: kl, MT_MAX_DOF sigma sums, used, clipped
+constexpr int kPpoExtras = MT_PPO_EXTRA_WORDS;
+constexpr float kLog2e = 1.44269504088896340736f;
+struct PpoGradArgs : PolicyGradArgs {  // coef / coef_ld: the advantages
+  const float* old_logp;  // [T][old_ld]
+  int64_t old_ld;
+  const float* weight;  // [T][weight_ld] or NULL
+  int64_t weight_ld;
+  float lo, hi, shift;  // the fp32 nearest to 1 -+ clip; log_ratio_shift
+  uint32_t clipping;    // clip > 0
+  float* ratio;         // [T][ratio_ld] or NULL
+  int64_t ratio_ld;
+  float* coef_out;  // [T][coefo_ld] or NULL
+  int64_t coefo_ld;
+  float* sigma_grad;  // [D] or NULL
+  float* kl;          // [1] or NULL
+  long long* count;   // [2] or NULL
+};
+template <int MODE>
+struct PolicyGradMode {
+  using Args = PolicyGradArgs;
+};
+template <>
+struct PolicyGradMode<1> {
+  using Args = PpoGradArgs;
+};
+// A lane's extra sums over its tiles, word q of thread tid at [q kBlock + tid]: in LDS, not in registers -- the kernel has
+// none to spare (profiles/ppo_grad_kernel_resources.md), and only the lane itself touches its words until the block adds
+// them up.  Only the PPO instantiations reach this function.
+__device__ __forceinline__ float* ppo_lane_sums() {
+  __shared__ float sums[kPpoExtras * kBlock];
+  return sums;
+}
 
 constexpr int kPolicyGradMaxIn = 3 * MT_MAX_TARGETS + MT_MAX_DOF;  // 104
 constexpr int kPolicyGradOutCols = 128;  // the output layer's tile: 8 rows x 32 threads x 4 columns
@@ -3166,8 +3210,8 @@ __device__ __forceinline__ void policy_grad_store(const PolicyGradOutTile& g, fl
   }
 }
 
-template <int W, int NCH0>
-__global__ __launch_bounds__(kBlock) void policy_grad_kernel(const PolicyGradArgs r) {
+template <int W, int NCH0, int MODE = 0>
+__global__ __launch_bounds__(kBlock) void policy_grad_kernel(const typename PolicyGradMode<MODE>::Args r) {
   using S = PolicyGradShape<W, NCH0>;
   __shared__ __attribute__((aligned(16))) float img[S::kWords];
   float* const A = img;
@@ -3183,6 +3227,10 @@ __global__ __launch_bounds__(kBlock) void policy_grad_kernel(const PolicyGradArg
   PolicyGradTile<W, NCH0> gh0{};      // hidden layer 0: L >= 2
   PolicyGradTile<W, 1> gh1{};         // hidden layer 1: L == 3
   float loss = 0.f;
+  if constexpr (MODE == 1) {
+#pragma unroll
+    for (int q = 0; q < kPpoExtras; ++q) ppo_lane_sums()[q * kBlock + threadIdx.x] = 0.f;  // (+0.f is the integer 0 too)
+  }
 
   for (int64_t tile = blockIdx.x; tile < r.tiles; tile += gridDim.x) {  // (block-uniform: every thread meets every barrier)
     const int64_t t = tile / r.tiles_per_step;
@@ -3190,6 +3238,9 @@ __global__ __launch_bounds__(kBlock) void policy_grad_kernel(const PolicyGradArg
     bool active = i < r.n;
     float c = 0.f, a[MT_MAX_DOF];
     if (active) c = r.coef[t * r.coef_ld + i];
+    if constexpr (MODE == 1) {  // c is A until the ratio is known
+      if (active && r.weight) c = r.weight[t * r.weight_ld + i] * c;
+    }
     active = active && c != 0.f;
     bool bad = false;
 #pragma unroll
@@ -3266,10 +3317,55 @@ __global__ __launch_bounds__(kBlock) void policy_grad_kernel(const PolicyGradArg
         const float e = a[j] - mu;
         const float d = e * r.inv_var[j];
         lp = __builtin_fmaf(e, d, lp);
-        dl[j] = ((c * d) * r.out_scale) * policy_act_slope(r.out_act, tj);
+        if constexpr (MODE == 0) {
+          dl[j] = ((c * d) * r.out_scale) * policy_act_slope(r.out_act, tj);
+        }
       }
     }
-    loss = __builtin_fmaf(c, -0.5f * lp, loss);
+    if constexpr (MODE == 0) {
+      loss = __builtin_fmaf(c, -0.5f * lp, loss);
+    } else {
+      const float adv = c;  // A: not 0 on an active lane
+      float ratio = 0.f;
+      c = 0.f;
+      if (active) {
+        const float x0 = (-0.5f * lp - r.old_logp[t * r.old_ld + i]) + r.shift;
+        const float x = fminf(fmaxf(x0, -MT_PPO_MAX_LOG_RATIO), MT_PPO_MAX_LOG_RATIO);
+        ratio = __builtin_amdgcn_exp2f(x * kLog2e);
+        const bool up = adv > 0.f;
+        const bool clipped = r.clipping && (up ? ratio > r.hi : ratio < r.lo);
+        const float ra = ratio * adv;
+        c = clipped ? 0.f : ra;
+        const float obj = clipped ? (up ? r.hi : r.lo) * adv : ra;
+        loss = loss + obj;
+        const float k = (ratio - 1.f) - x;
+        float* const ls = ppo_lane_sums() + threadIdx.x;  // kl, MT_MAX_DOF sigma sums, used, clipped
+        ls[0] = ls[0] + k;
+        int* const used = reinterpret_cast<int*>(ls + (1 + MT_MAX_DOF) * kBlock);
+        used[0] += 1;
+        used[kBlock] += clipped ? 1 : 0;
+      }
+#pragma unroll
+      for (int j = 0; j < MT_MAX_DOF; ++j) {
+        if (j < D) {
+          // e and d once more, by the loop's own expressions from a y the compiler cannot tell from a new one: kept across
+          // the ratio they would be 3 D more live registers where the kernel has none
+          float yj = y[j];
+          asm volatile("" : "+v"(yj));
+          const float tj = policy_act(r.out_act, yj);
+          const float mu = r.out_scale * tj;
+          const float e = a[j] - mu;
+          const float d = e * r.inv_var[j];
+          dl[j] = ((c * d) * r.out_scale) * policy_act_slope(r.out_act, tj);
+          float* const sg = ppo_lane_sums() + (1 + j) * kBlock + threadIdx.x;
+          sg[0] = __builtin_fmaf(c, __builtin_fmaf(e, d, -1.f), sg[0]);
+        }
+      }
+      if (i < r.n) {
+        if (r.ratio) r.ratio[t * r.ratio_ld + i] = ratio;
+        if (r.coef_out) r.coef_out[t * r.coefo_ld + i] = c;
+      }
+    }
 
     if (L == 1) {
       reduce(gout, dl, put_x, IN, D);
@@ -3295,17 +3391,34 @@ __global__ __launch_bounds__(kBlock) void policy_grad_kernel(const PolicyGradArg
     }
   }
 
-  float* part = r.partials + (int64_t)blockIdx.x * (r.P + 1);
+  float* part = r.partials + (int64_t)blockIdx.x * (r.P + 1 + (MODE == 1 ? kPpoExtras : 0));
   policy_grad_store(gout, part + r.off[L - 1], r.n_in[L - 1], D);
   if (L >= 2) policy_grad_store(gh0, part + r.off[0], IN, r.n_out[0]);
   if (L == 3) policy_grad_store(gh1, part + r.off[1], r.n_in[1], r.n_out[1]);
   __syncthreads();
-  img[threadIdx.x] = loss;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float s = 0.f;
-    for (int q = 0; q < kBlock; ++q) s = s + img[q];
-    part[r.P] = s;
+  if constexpr (MODE == 0) {
+    img[threadIdx.x] = loss;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float s = 0.f;
+      for (int q = 0; q < kBlock; ++q) s = s + img[q];
+      part[r.P] = s;
+    }
+  } else {  // thread 0 adds the objective, thread q > 0 the lanes' extra sum q - 1, each in thread order
+    img[threadIdx.x] = loss;
+    __syncthreads();
+    if (threadIdx.x < 1 + kPpoExtras) {
+      const float* col = threadIdx.x ? ppo_lane_sums() + (threadIdx.x - 1) * kBlock : img;
+      if (threadIdx.x < 2 + MT_MAX_DOF) {
+        float s = 0.f;
+        for (int q = 0; q < kBlock; ++q) s = s + col[q];
+        part[r.P + threadIdx.x] = s;
+      } else {  // a block's counts fit 32 bits: it sees at most max(kBlock, samples / blocks) samples
+        int s = 0;
+        for (int q = 0; q < kBlock; ++q) s += __float_as_int(col[q]);
+        part[r.P + threadIdx.x] = __int_as_float(s);
+      }
+    }
   }
 }
 
@@ -3318,6 +3431,27 @@ __global__ __launch_bounds__(kBlock) void policy_grad_reduce_kernel(const Policy
   s = s * r.scale;
   if (i < r.P) r.grad[i] = s;
   else if (r.loss) r.loss[0] = s;
+}
+
+// mt_ppo_grad's second pass: the same sums over rows of P + 1 + kPpoExtras words; the last two words are integer counts
+__global__ __launch_bounds__(kBlock) void ppo_grad_reduce_kernel(const PpoGradArgs r) {
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  const int64_t pitch = r.P + 1 + kPpoExtras;
+  if (i >= pitch) return;
+  const int64_t e = i - r.P;  // 0: the objective, 1: kl, 2 .. 1 + MT_MAX_DOF: sigma, then used, clipped
+  if (e >= 2 + MT_MAX_DOF) {
+    long long s = 0;
+    for (int b = 0; b < r.blocks; ++b) s += (long long)__float_as_int(r.partials[(int64_t)b * pitch + i]);
+    if (r.count) r.count[e - (2 + MT_MAX_DOF)] = s;
+    return;
+  }
+  float s = 0.f;
+  for (int b = 0; b < r.blocks; ++b) s = s + r.partials[(int64_t)b * pitch + i];
+  s = s * r.scale;
+  if (i < r.P) r.grad[i] = s;
+  else if (e == 0) { if (r.loss) r.loss[0] = s; }
+  else if (e == 1) { if (r.kl) r.kl[0] = s; }
+  else if (e - 2 < r.D && r.sigma_grad) r.sigma_grad[e - 2] = s;
 }
 
 struct RewardToGoArgs {

@@ -931,7 +931,8 @@ class StepEngine:
         return out
 
     def policy_grad(self, layers_or_theta, obs, actions, coef, *, sigma, widths=(), hidden="tanh", out="tanh", out_scale=180.0,
-                    see_pose=False, scale=1.0, grad_out=None, loss=False):
+                    see_pose=False, scale=1.0, grad_out=None, loss=False, old_logp=None, clip=0.2, weights=None, sigma_old=None,
+                    ratio=False, coef_out=False, sigma_grad=False):
         """grad = scale * sum over samples (t, i) of coef[t, i] * d logp / d theta (mt_policy_grad), logp = -1/2 sum_j
         ((actions[t, j, i] - mu_j(obs[t, :, i])) / sigma_j)^2, mu the policy's action before noise and clamp -- the
         REINFORCE direction with coef = reward_to_go(...), behaviour cloning with coef = 1, sigma = 1.  `layers_or_theta`: a
@@ -942,7 +943,22 @@ class StepEngine:
         (P,) float32 in flatten_policy's layout (written into `grad_out` when given), so theta += lr * grad ascends; with
         loss=True (grad, loss), loss a (1,) tensor holding scale * sum coef * logp.  Deterministic: the same arguments give
         the same bits.  Two launches, no host wait; the workspace is cached on the engine.  Stream behaviour as
-        rollout_actions; nothing resident is read or written."""
+        rollout_actions; nothing resident is read or written.
+
+        With old_logp= (T, N), policy_eval's logp when the actions were taken, the call is PPO's clipped surrogate in one
+        pass (mt_ppo_grad): the positional `coef` holds the ADVANTAGES, `weights` (T, N) or None multiplies them (gae's
+        `weights`), ratio = exp(logp_now - old_logp) is formed in the kernel and a sample counts with ratio * advantage
+        unless it is clipped (advantage > 0 and ratio > 1 + clip, or advantage < 0 and ratio < 1 - clip); clip=0 never
+        clips.  sigma_old: the sigma old_logp was taken with, when it differs from `sigma` (the dropped normalisers then
+        enter the ratio).  Returns a dict of device tensors, no host sync: `grad` (P,), `loss` (1,) = scale * sum of
+        min(ratio A, clamp(ratio) A), `kl` (1,) = scale * sum of (ratio - 1) - log ratio, `used` and `clipped` (int64
+        scalars: the samples that count and, of them, the clipped ones) and, on request, `ratio` and `coef` (T, N; ratio=True
+        / coef_out=True, or tensors to write into) and `sigma_grad` (D,) = scale * sum of coef * d logp / d log sigma_j
+        (sigma_grad=True).  grad is bit for bit policy_grad(coef=that `coef`)."""
+        if old_logp is not None:
+            return self._ppo_grad(layers_or_theta, obs, actions, coef, old_logp, sigma=sigma, widths=widths, hidden=hidden, out=out,
+                                  out_scale=out_scale, see_pose=see_pose, scale=scale, grad_out=grad_out, clip=clip, weights=weights,
+                                  sigma_old=sigma_old, ratio=ratio, coef_out=coef_out, sigma_grad=sigma_grad)
         import torch
         dev = torch.device("cuda", self.device)
         d = self.dof
@@ -984,6 +1000,81 @@ class StepEngine:
         self._torch_call(self._lib.mt_policy_grad, C.byref(arg), commits=False)
         del keep
         return (grad_out, loss_t) if loss else grad_out
+
+    def _ppo_grad(self, layers_or_theta, obs, actions, adv, old_logp, *, sigma, widths, hidden, out, out_scale, see_pose, scale,
+                  grad_out, clip, weights, sigma_old, ratio, coef_out, sigma_grad):
+        """policy_grad(..., old_logp=): mt_ppo_grad."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        d, n = self.dof, self.n_envs
+        arg = L.MtPpoGrad()
+        keep, n_layers, n_in, p = self._policy_net_arg(arg, layers_or_theta, widths, hidden, out, see_pose, d)
+        sig = np.ones(L.MT_MAX_DOF, dtype=np.float32)
+        sig[:d] = np.broadcast_to(np.asarray(sigma, dtype=np.float32), (d,))
+        if not (np.isfinite(sig).all() and (sig > 0).all()):
+            raise ValueError(f"sigma must be finite and > 0, got {sigma!r}")
+        shift = 0.0
+        if sigma_old is not None:
+            old = np.broadcast_to(np.asarray(sigma_old, dtype=np.float32), (d,)).astype(np.float64)
+            if not (np.isfinite(old).all() and (old > 0).all()):
+                raise ValueError(f"sigma_old must be finite and > 0, got {sigma_old!r}")
+            shift = float(np.log(old / sig[:d].astype(np.float64)).sum())
+        if not (np.isfinite(np.float32(scale)) and np.isfinite(np.float32(out_scale)) and np.isfinite(np.float32(shift))):
+            raise ValueError("scale, out_scale and the shift of sigma_old must be finite")
+        clip = float(np.float32(clip))
+        if not (clip == 0.0 or 0.0 < clip < 1.0):
+            raise ValueError(f"clip must be 0 (no clipping) or in (0, 1), got {clip!r}")
+        T, obs_ld = self._log_rows(obs, "obs", n_in, torch.float32)
+        Ta, act_ld = self._log_rows(actions, "actions", d, torch.float32)
+        Tc, adv_ld = self._log_rows(adv, "coef", None, torch.float32)
+        To, old_ld = self._log_rows(old_logp, "old_logp", None, torch.float32)
+        Tw, weight_ld = self._log_rows(weights, "weights", None, torch.float32) if weights is not None else (T, n)
+        if not T == Ta == Tc == To == Tw:
+            raise ValueError(f"obs, actions, coef, old_logp and weights must have the same number of steps, got {T}, {Ta}, {Tc}, {To}, {Tw}")
+        if grad_out is None:
+            grad_out = torch.empty(p, dtype=torch.float32, device=dev)
+        else:
+            self._flat_vector(grad_out, "grad_out", p)
+        small = torch.zeros(2, dtype=torch.float32, device=dev)         # loss, kl
+        count = torch.zeros(2, dtype=torch.int64, device=dev)           # used, clipped
+        res = {"grad": grad_out, "loss": small[0:1], "kl": small[1:2], "used": count[0], "clipped": count[1]}
+        arg.struct_size = C.sizeof(L.MtPpoGrad)
+        arg.n_steps, arg.n_layers = T, n_layers
+        arg.hidden_act, arg.out_act = self._ACTIVATIONS[hidden], self._ACTIVATIONS[out]
+        arg.out_scale, arg.scale = float(out_scale), float(scale)
+        arg.clip, arg.log_ratio_shift = clip, shift
+        arg.sigma[:] = sig.tolist()
+        arg.flags = L.POLICY_SEE_POSE if see_pose else 0
+        arg.obs, arg.action, arg.adv, arg.old_logp = ((obs.data_ptr(), actions.data_ptr(), adv.data_ptr(), old_logp.data_ptr()) if T
+                                                      else (None, None, None, None))
+        arg.sample_weight = weights.data_ptr() if weights is not None and T else None
+        arg.obs_ld, arg.act_ld, arg.adv_ld, arg.old_ld, arg.weight_ld = obs_ld, act_ld, adv_ld, old_ld, weight_ld
+        for key, want, name, field, ld_field in (("ratio", ratio, "ratio", "ratio_out", "ratio_ld"),
+                                                 ("coef", coef_out, "coef_out", "coef_out", "coef_ld")):
+            given = _is_torch_tensor(want)
+            if not (given or want):
+                continue
+            res[key] = want if given else torch.empty((T, n), dtype=torch.float32, device=dev)
+            To, ld = self._log_rows(res[key], name, None, torch.float32)
+            if To != T:
+                raise ValueError(f"{name} must have T = {T} rows")
+            setattr(arg, field, res[key].data_ptr() if T else None)
+            setattr(arg, ld_field, ld)
+        if sigma_grad:
+            res["sigma_grad"] = torch.zeros(d, dtype=torch.float32, device=dev)
+            arg.sigma_grad_out = res["sigma_grad"].data_ptr()
+        arg.grad_out = grad_out.data_ptr()
+        arg.loss_out, arg.kl_out, arg.count_out = res["loss"].data_ptr(), res["kl"].data_ptr(), count.data_ptr()
+        need = int(self._lib.mt_ppo_grad_workspace(self._h, n_layers, arg.width, arg.flags, T))
+        ws = getattr(self, "_ppo_workspace", None)
+        if need and (ws is None or ws.numel() * 4 < need):
+            ws = self._ppo_workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
+        arg.workspace = ws.data_ptr() if need else None
+        arg.workspace_bytes = ws.numel() * 4 if need else 0
+        arg.reserved = 0
+        self._torch_call(self._lib.mt_ppo_grad, C.byref(arg), commits=False)
+        del keep
+        return res
 
     # ---- a critic and GAE weights: the forward pass over the logs, the advantages, the value head's gradient ---------------
     def policy_eval(self, layers_or_theta, obs, *, actions=None, sigma=None, n_out=None, widths=(), hidden="tanh", out="tanh",
