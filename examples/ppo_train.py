@@ -2,9 +2,11 @@
 """PPO (clipped surrogate, GAE) on a small MLP policy and an MLP critic without torch autograd anywhere and without a
 transposed copy of the logs: every pass over the samples is one engine call on the logs as rollout_policy wrote them.
 
-  1. rollout_policy(sigma=s, actions=True, observations=True, log=True): T steps, Gaussian exploration in-kernel
-  2. policy_eval(theta, obs, actions=, sigma=s): log pi_old(a | x) per sample; values(phi, obs): V(x) per sample; the
-     bootstrap V(x_T) from observe() and the resident observation rows, read in place as a one-step block
+  1. rollout_policy(sigma=s, actions=True, observations=True, log=True, logp=True, critic=phi's layers): T steps, Gaussian
+     exploration in-kernel, and from the SAME launch log pi_old(a | x) and V(x) per sample and the bootstrap V(x_T)
+  2. (--collect parts: the four calls that launch replaces, whose results are the same bit for bit -- policy_eval(theta, obs,
+     actions=, sigma=s) for log pi_old, values(phi, obs) for V, observe() and values on the resident observation rows, read
+     in place as a one-step block, for V(x_T))
   3. gae(reward, done, V, last_value=V(x_T), mask_after_done=True, weights=True): advantages, value targets, and the
      weights that take the steps behind an env's episode end out of both gradients
   4. a few epochs of: policy_grad(adv, old_logp=, clip=, weights=) -- the new log pi, the ratio, the clip decision and the
@@ -39,6 +41,8 @@ ap.add_argument("--clip", type=float, default=0.2)
 ap.add_argument("--lr", type=float, default=0.0003, help="length of the policy's step: theta += lr * grad / |grad|")
 ap.add_argument("--value-lr", type=float, default=0.02, help="length of the critic's step")
 ap.add_argument("--seed", type=int, default=1)
+ap.add_argument("--collect", choices=("fused", "parts"), default="fused",
+                help="fused: logp, values and the bootstrap value from the rollout's launch; parts: the four calls it replaces")
 ap.add_argument("--parts", action="store_true", help="policy_eval + four torch lines + policy_grad instead of the one fused call")
 args = ap.parse_args()
 
@@ -62,13 +66,18 @@ pi = dict(sigma=args.sigma, widths=widths, out_scale=179.0)
 
 for it in range(args.iterations):
     eng.reset_random(seed=args.seed, episode=it)
+    fused = args.collect == "fused"
+    ac = dict(logp=True, critic=eng.unflatten_value(phi, widths)) if fused else {}
     log = eng.rollout_policy(eng.unflatten_policy(theta, widths), args.steps, sigma=args.sigma, draw=it, seed=args.seed,
-                             out_scale=179.0, log=True, returns=True, actions=True, observations=True)
+                             out_scale=179.0, log=True, returns=True, actions=True, observations=True, **ac)
     obs, actions = log["observations"], log["actions"]
-    old = eng.policy_eval(theta, obs, actions=actions, mean=False, **pi)["logp"]
-    values = eng.values(phi, obs, widths=widths)
-    eng.observe()                                    # x_T: the observation of the state the last step left
-    last = eng.values(phi, eng.device_tensor(m.lib.F_OBS)[None], widths=widths)[0]
+    if fused:
+        old, values, last = log["logp"], log["values"], log["last_value"]
+    else:
+        old = eng.policy_eval(theta, obs, actions=actions, mean=False, **pi)["logp"]
+        values = eng.values(phi, obs, widths=widths)
+        eng.observe()                                # x_T: the observation of the state the last step left
+        last = eng.values(phi, eng.device_tensor(m.lib.F_OBS)[None], widths=widths)[0]
     est = eng.gae(log["reward"], log["done"], values, last_value=last, gamma=args.gamma, lam=args.lam, mask_after_done=True,
                   weights=True)
     adv, returns, weights = est["advantages"], est["returns"], est["weights"]

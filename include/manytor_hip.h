@@ -41,7 +41,7 @@ extern "C" {
 #define MT_API
 #endif
 
-#define MT_VERSION 490       /* major*10000 + minor*100 + patch */
+#define MT_VERSION 500      /* major*10000 + minor*100 + patch */
 #define MT_MAX_DOF 8
 #define MT_MAX_TARGETS 32
 #define MT_MAX_RETURN_RING 64
@@ -476,6 +476,45 @@ struct mt_policy {         /* as with mt_cem, the type is always written `struct
   uint64_t reserved;       /* must be 0 */
 };
 MT_API int mt_rollout_policy(mt_handle h, const struct mt_policy* p);
+
+/* mt_rollout_policy with what an actor-critic collection wants from the same launch: the log-probability of every action
+ * under the policy that drew it, and a critic's value of every state, the one behind the last step included.
+ *
+ * Resident state.  `policy` is mt_rollout_policy's argument, its own struct_size included, and everything that call does
+ * for it this call does, bit for bit: every field, the logs, return_out, ring / MT_F_LAST_RETURN / MT_F_EPISODES,
+ * mt_bad_action_count, the flags, the refusals (their messages name mt_actor_critic.policy).
+ * logp_log[t, i] is mt_policy_eval's logp_out for x = obs_log[t, :, i], a = action_log[t, :, i], the policy's weights and
+ * policy.sigma, bit for bit: e = a_j - mu_j, d = e * inv_var_j, lp = fmaf(e, d, lp) for ascending j, -0.5f * lp, with
+ * inv_var_j the fp32 nearest to 1 / sigma_j^2, mu_j the mean in front of the noise and a_j what action_log gets; a sample
+ * whose action is unusable gets exactly 0.  With logp_log every sigma_j, j < D, must be finite and > 0.  Neither obs_log
+ * nor action_log has to be given.
+ * The critic is an MLP of the policy's shape and limits whose last layer has ONE output, on the same x (IN as the policy's,
+ * MT_POLICY_SEE_POSE included): value_log[t, i] is mt_policy_eval's mean_out with n_out = 1 for it, bit for bit, and
+ * last_value_out[i] the same for x_T, the input a step T would start from (after a re-arm in the last step: the zero pose
+ * with the new targets).  last_value_out is written by a dry run too.
+ * With a critic the kernel keeps x of a block in LDS behind the targets: 3 K + IN <= MT_ACTOR_CRITIC_MAX_LDS / 1024 = 160,
+ * that is K <= 26 without MT_POLICY_SEE_POSE; a handle beyond that gets MT_ERR_UNSUPPORTED (logp_log alone has no limit).
+ * critic_layers == 0 with value_log or last_value_out, and a call with neither a critic nor logp_log (which is
+ * mt_rollout_policy), are MT_ERR_INVALID_ARG; so are an ld below n_envs and any overlap of the three outputs with the
+ * weights of either network, with the policy's logs or with each other.  n_steps == 0 is a no-op: nothing is written.
+ * One launch on the handle's stream, no allocation, no host wait: legal under stream capture. */
+#define MT_ACTOR_CRITIC_MAX_LDS 163840   /* bytes of LDS a block may hold: (3 K + IN) * 256 lanes * 4 */
+struct mt_actor_critic {   /* as with mt_cem, the type is always written `struct mt_actor_critic` */
+  int32_t struct_size;     /* = sizeof(struct mt_actor_critic), checked */
+  int32_t critic_layers;   /* 0 = no critic, else 1..MT_POLICY_MAX_LAYERS */
+  struct mt_policy policy; /* everything mt_rollout_policy reads; policy.struct_size = sizeof(struct mt_policy), checked */
+  int32_t critic_width[2]; /* hidden widths of the critic, each 1..MT_POLICY_MAX_WIDTH */
+  int32_t critic_hidden_act, critic_out_act;   /* as mt_value_grad: out is MT_ACT_IDENTITY or MT_ACT_TANH */
+  const float* critic_weight[3];   /* DEVICE f32 (out, in); the last layer is (1, in) */
+  const float* critic_bias[3];     /* DEVICE f32 (out,) */
+  float critic_out_scale;  /* V = critic_out_scale * critic_out_act(y), finite */
+  uint32_t pad_;           /* (not read) */
+  float* logp_log;   int64_t logp_ld;    /* DEVICE or NULL: (T, logp_ld) */
+  float* value_log;  int64_t value_ld;   /* DEVICE or NULL: (T, value_ld); needs a critic */
+  float* last_value_out;                 /* DEVICE or NULL: (n_envs,); needs a critic */
+  uint64_t reserved;       /* must be 0 */
+};
+MT_API int mt_rollout_actor_critic(mt_handle h, const struct mt_actor_critic* p);
 
 /* An evolution-strategies generation: the planners' three levels (mt_sample_plans; mt_shoot; mt_cem / mt_mppi) in
  * PARAMETER space -- mt_es_sample perturbs, mt_rollout_population scores, mt_es runs the generation in one call.

@@ -245,6 +245,31 @@ POLICY_MAX_WIDTH = 64
 ACT_IDENTITY, ACT_TANH, ACT_RELU = 0, 1, 2
 
 
+class MtActorCritic(C.Structure):
+    """struct mt_actor_critic of include/manytor_hip.h: the argument block of mt_rollout_actor_critic."""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("critic_layers", C.c_int32),
+        ("policy", MtPolicy),
+        ("critic_width", C.c_int32 * 2),
+        ("critic_hidden_act", C.c_int32),
+        ("critic_out_act", C.c_int32),
+        ("critic_weight", C.c_void_p * 3),
+        ("critic_bias", C.c_void_p * 3),
+        ("critic_out_scale", C.c_float),
+        ("pad_", C.c_uint32),
+        ("logp_log", C.c_void_p),
+        ("logp_ld", C.c_int64),
+        ("value_log", C.c_void_p),
+        ("value_ld", C.c_int64),
+        ("last_value_out", C.c_void_p),
+        ("reserved", C.c_uint64),
+    ]
+
+
+ACTOR_CRITIC_MAX_LDS = 163840
+
+
 class MtEsSample(C.Structure):
     """struct mt_es_sample of include/manytor_hip.h: the argument block of mt_es_sample."""
     _fields_ = [
@@ -552,6 +577,7 @@ PROTOTYPES = {
     "mt_sample_plans": (C.c_int, [_HANDLE, C.POINTER(MtCem), C.c_void_p, C.c_int64, C.c_int64]),
     "mt_mppi": (C.c_int, [_HANDLE, C.POINTER(MtMppi)]),
     "mt_rollout_policy": (C.c_int, [_HANDLE, C.POINTER(MtPolicy)]),
+    "mt_rollout_actor_critic": (C.c_int, [_HANDLE, C.POINTER(MtActorCritic)]),
     "mt_es_sample": (C.c_int, [_HANDLE, C.POINTER(MtEsSample)]),
     "mt_rollout_population": (C.c_int, [_HANDLE, C.POINTER(MtPopulation)]),
     "mt_es": (C.c_int, [_HANDLE, C.POINTER(MtEs)]),

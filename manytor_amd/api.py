@@ -347,6 +347,15 @@ class Multienv:
                     [[bool(d) for d in row] for row in done])
         return BatchView(e, L.F_OBS), rew, done
 
+    def collect_policy(self, layers, steps, **kw):
+        """run_policy for an actor-critic loop: the same `steps` step()s in one launch, returning StepEngine.rollout_policy's
+        dict of device tensors as it is (its keywords: log, actions, observations, returns, logp=True, critic=...; no
+        host copy, no wait).  The envs move as under run_policy unless dry_run=True."""
+        res = self._engine.rollout_policy(layers, steps, **kw)
+        if not kw.get("dry_run"):
+            self._step_idx += int(steps)
+        return res
+
     def evolve_policy(self, theta, sigma, members, steps, **kw):
         """One evolution-strategies generation on the batch in one call (StepEngine.es, which documents the keywords):
         `members` antithetic perturbations of the flat policy parameters `theta`, each scored on its own n_envs / members

@@ -9,13 +9,15 @@ import os
 import shutil
 import subprocess
 import sys
+import tempfile
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 INCLUDE = os.path.join(os.path.dirname(PKG_DIR), "include")
 LIB_PATH = os.path.join(PKG_DIR, "libmanytor_hip.so")
-SOURCES = ["engine.hip", "comm.hip"]
-DEPS = ["engine.hip", "comm.hip", "engine_internal.h", "step_args.h", "kernels.h", "mt_math.h", "philox.h"]
+# one compiler process per source, side by side: engine.hip and actor_critic.hip hold the large kernel families
+SOURCES = ["engine.hip", "actor_critic.hip", "comm.hip"]
+DEPS = SOURCES + ["engine_internal.h", "step_args.h", "kernels.h", "table_dispatch.h", "mt_math.h", "philox.h"]
 
 
 EXTRA_FLAGS = [
@@ -48,17 +50,24 @@ def is_stale() -> bool:
 def build_library(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
     if not force and not is_stale():
         return LIB_PATH
-    cmd = [
-        _hipcc(), "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared", "-fvisibility=hidden",
-        "-I", INCLUDE, "-Wall", "-Wno-unused-function",
-        *EXTRA_FLAGS,
-        *extra_flags,
-        *[os.path.join(CSRC, s) for s in SOURCES],
-        "-o", LIB_PATH + ".tmp",
-    ]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.run(cmd, check=True)
+    flags = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-I", INCLUDE, "-Wall",
+             "-Wno-unused-function", *EXTRA_FLAGS, *extra_flags]
+    with tempfile.TemporaryDirectory(prefix="manytor_build_") as tmp:
+        jobs = []
+        for src in SOURCES:
+            obj = os.path.join(tmp, os.path.splitext(src)[0] + ".o")
+            cmd = [_hipcc(), *flags, "-c", os.path.join(CSRC, src), "-o", obj]
+            if verbose:
+                print(" ".join(cmd), flush=True)
+            jobs.append((cmd, obj, subprocess.Popen(cmd)))
+        failed = [cmd for cmd, _, proc in jobs if proc.wait() != 0]      # (every process is waited for)
+        if failed:
+            raise subprocess.CalledProcessError(1, failed[0])
+        link = [_hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", "-fvisibility=hidden", *[obj for _, obj, _ in jobs],
+                "-o", LIB_PATH + ".tmp"]
+        if verbose:
+            print(" ".join(link), flush=True)
+        subprocess.run(link, check=True)
     os.replace(LIB_PATH + ".tmp", LIB_PATH)
     return LIB_PATH
 

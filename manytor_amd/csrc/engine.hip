@@ -19,6 +19,7 @@
 
 #include "engine_internal.h"
 #include "kernels.h"
+#include "table_dispatch.h"
 
 using namespace mt;
 
@@ -922,26 +923,6 @@ void launch_tape(mt_handle h, const StepArgs& a, const TapeArgs& r) {
 }
 
 // f(TableTag<Tbl>{}) with the handle's table type: the kernels of the planner calls have no other compile-time axis.
-template <class Tbl>
-struct TableTag {
-  using type = Tbl;
-};
-template <class F>
-void with_table(const mt_engine* h, F&& f) {
-  if (h->static_kind == 1) return f(TableTag<Ref4Table>{});
-  if (h->static_kind == 2) return f(TableTag<Dh7Table>{});
-  switch (h->D) {
-    case 2: return f(TableTag<RtTable<2>>{});
-    case 3: return f(TableTag<RtTable<3>>{});
-    case 4: return f(TableTag<RtTable<4>>{});
-    case 5: return f(TableTag<RtTable<5>>{});
-    case 6: return f(TableTag<RtTable<6>>{});
-    case 7: return f(TableTag<RtTable<7>>{});
-    case 8: return f(TableTag<RtTable<8>>{});
-    default: return;
-  }
-}
-
 // mt_shoot's commit: rollout_tape_kernel with every env following the plane its evaluation chose (SELECT).  One form, no
 // next-step prefetch (it was measured for the plain tape only).
 template <class Tbl>
@@ -973,7 +954,6 @@ void launch_policy(mt_handle h, const StepArgs& a, const PolicyArgs& r, int widt
     launch_policy_t<Tbl, 64>(h, a, r);
   });
 }
-
 
 // shoot_kernel on the whole batch: a block per 64 envs, its four waves share the candidates (kernels.h).
 template <class Tbl>
@@ -2415,7 +2395,10 @@ static int rollout_policy_screen(mt_handle h, const struct mt_policy* p, const s
 }
 // ... the launch (the caller has entered the handle: MT_ENTER): block b reads the weights of member b / blocks_per_member,
 // member_pitch floats behind member 0's
-static int rollout_policy_run(mt_handle h, const struct mt_policy* p, const PolicyScreen& sc, uint32_t blocks_per_member, int64_t member_pitch) {
+// `ac` (mt_rollout_actor_critic): what the launch writes besides, its PolicyArgs part filled in here; `ac_widest` the
+// critic's widest hidden layer
+static int rollout_policy_run(mt_handle h, const struct mt_policy* p, const PolicyScreen& sc, uint32_t blocks_per_member, int64_t member_pitch,
+                              ActorCriticArgs* ac = nullptr, int ac_widest = 0) {
   const bool auto_reset = (p->flags & MT_POLICY_AUTO_RESET) != 0, dry = (p->flags & MT_POLICY_DRY_RUN) != 0;
   const int L = p->n_layers, widest = sc.widest;
   const bool noisy = sc.noisy;
@@ -2460,7 +2443,12 @@ static int rollout_policy_run(mt_handle h, const struct mt_policy* p, const Poli
     int rcg = order_behind_inplace_gather(h, h->stream);
     if (rcg) return rcg;
   }
-  launch_policy(h, h->args, r, widest);
+  if (ac) {
+    static_cast<PolicyArgs&>(*ac) = r;
+    launch_actor_critic(h, h->args, *ac, std::max(widest, ac_widest));
+  } else {
+    launch_policy(h, h->args, r, widest);
+  }
   if (!dry) {
     h->args.flags &= ~kFlagWholeGoals;  // a policy's angles are anybody's floats
     h->codes_valid = false;             // the kernel writes targets as floats only
@@ -3104,6 +3092,101 @@ int mt_policy_eval(mt_handle h, const struct mt_policy_eval* p) {
   else
     hipLaunchKernelGGL((policy_eval_kernel<64>), grid, dim3(kBlock), 0, h->stream, r);
   return check_launch(h, "policy_eval_kernel");
+}
+
+// mt_rollout_policy's launch with logp and a critic's values written beside its logs: the policy's screen and launch path
+// (rollout_policy_screen, rollout_policy_run), the critic's shape through policy_layout with one output.
+int mt_rollout_actor_critic(mt_handle h, const struct mt_actor_critic* p) {
+  MT_REQUIRE(h, p != nullptr, "actor_critic is NULL");  // (the struct first: its size is checked with or without a handle)
+  MT_REQUIRE(h, p->struct_size == (int32_t)sizeof(struct mt_actor_critic), "mt_actor_critic.struct_size does not match this library");
+  MT_REQUIRE(h, p->policy.struct_size == (int32_t)sizeof(struct mt_policy), "mt_actor_critic.policy.struct_size does not match this library");
+  const std::string w = "mt_actor_critic";
+  MT_REQUIRE(h, p->reserved == 0, w + ".reserved must be 0");
+  MT_REQUIRE(h, p->policy.reserved == 0, w + ".policy.reserved must be 0");
+  const int CL = p->critic_layers;
+  MT_REQUIRE(h, CL >= 0 && CL <= MT_POLICY_MAX_LAYERS, w + ".critic_layers must be 0 (no critic) or 1.." + std::to_string(MT_POLICY_MAX_LAYERS));
+  int c_widest = 0;
+  for (int l = 0; l + 1 < CL; ++l) {
+    MT_REQUIRE(h, p->critic_width[l] >= 1 && p->critic_width[l] <= MT_POLICY_MAX_WIDTH,
+               w + ".critic_width[" + std::to_string(l) + "] must be 1.." + std::to_string(MT_POLICY_MAX_WIDTH));
+    c_widest = std::max(c_widest, (int)p->critic_width[l]);
+  }
+  if (CL) {
+    MT_REQUIRE(h, CL == 1 || p->critic_hidden_act == MT_ACT_TANH || p->critic_hidden_act == MT_ACT_RELU,
+               w + ".critic_hidden_act must be MT_ACT_TANH or MT_ACT_RELU");
+    MT_REQUIRE(h, p->critic_out_act == MT_ACT_TANH || p->critic_out_act == MT_ACT_IDENTITY,
+               w + ".critic_out_act must be MT_ACT_TANH or MT_ACT_IDENTITY");
+    MT_REQUIRE(h, first_unusable(&p->critic_out_scale, 1, kMaxFiniteBits) < 0, w + ".critic_out_scale must be finite");
+  }
+  MT_REQUIRE(h, CL || !p->value_log, w + ".value_log needs a critic (critic_layers is 0)");
+  MT_REQUIRE(h, CL || !p->last_value_out, w + ".last_value_out needs a critic (critic_layers is 0)");
+  MT_REQUIRE(h, CL || p->logp_log, w + ": no critic and no logp_log: that call is mt_rollout_policy");
+  int rc;
+  if (p->logp_log && (rc = policy_sigma_screen(h, p->policy.sigma, 1, w + ".policy"))) return rc;
+  MT_REQUIRE(nullptr, h != nullptr, "handle is NULL");
+  const struct mt_policy* q = &p->policy;
+  PolicyScreen sc;
+  rc = rollout_policy_screen(h, q, w + ".policy", "mt_rollout_actor_critic", &sc);
+  if (rc || q->n_steps == 0) return rc;
+  if (p->logp_log)
+    for (int j = 0; j < h->D; ++j)
+      MT_REQUIRE(h, q->sigma[j] > 0.f, w + ".policy.sigma[" + std::to_string(j) + "] must be finite and > 0 with logp_log");
+  const int T = q->n_steps, D = h->D;
+  const int64_t n = h->n;
+  const uint32_t see_pose = q->flags & MT_POLICY_SEE_POSE;
+  PolicyLayout ps, cs{};
+  MT_REQUIRE(h, policy_layout(h, q->n_layers, q->width, see_pose, &ps), w + ".policy: not a policy shape");
+  const int IN = ps.n_in[0];
+  if (CL) {
+    MT_REQUIRE(h, policy_layout(h, CL, p->critic_width, see_pose, &cs, 1), w + ": not a critic shape");
+    for (int l = 0; l < CL; ++l)
+      MT_REQUIRE(h, p->critic_weight[l] != nullptr && p->critic_bias[l] != nullptr, w + ".critic_weight / critic_bias [" + std::to_string(l) + "] is NULL");
+    // the lanes' x columns share the block's LDS with the target tile
+    if (actor_critic_lds(h, IN, true) > (size_t)MT_ACTOR_CRITIC_MAX_LDS)
+      return fail(h, MT_ERR_UNSUPPORTED,
+                  "mt_rollout_actor_critic: a critic needs 3 K + IN <= " + std::to_string(MT_ACTOR_CRITIC_MAX_LDS / (kBlock * 4)) +
+                      " (the targets and x of a block in LDS); this handle has 3 K + IN = " + std::to_string(3 * h->K + IN));
+  }
+  MT_REQUIRE(h, !p->logp_log || p->logp_ld >= n, w + ".logp_ld is smaller than n_envs");
+  MT_REQUIRE(h, !p->value_log || p->value_ld >= n, w + ".value_ld is smaller than n_envs");
+  const Span out[3] = {{p->logp_log, p->logp_log ? rows_bytes(T, p->logp_ld, n) : 0, "logp_log"},
+                       {p->value_log, p->value_log ? rows_bytes(T, p->value_ld, n) : 0, "value_log"},
+                       {p->last_value_out, p->last_value_out ? (size_t)n * 4 : 0, "last_value_out"}};
+  const Span logs[5] = {{q->action_log, q->action_log ? rows_bytes((int64_t)T * D, q->act_ld, n) : 0, "policy.action_log"},
+                        {q->obs_log, q->obs_log ? rows_bytes((int64_t)T * IN, q->obs_ld, n) : 0, "policy.obs_log"},
+                        {q->reward_log, q->reward_log ? rows_bytes(T, q->log_ld, n, 1) : 0, "policy.reward_log"},
+                        {q->done_log, q->done_log ? rows_bytes(T, q->log_ld, n, 1) : 0, "policy.done_log"},
+                        {q->return_out, q->return_out ? (size_t)n * 4 : 0, "policy.return_out"}};
+  PolicyNet pnet{};
+  pnet.n_layers = q->n_layers;
+  pnet.weight = q->weight;
+  pnet.bias = q->bias;
+  if ((rc = policy_overlap_screen(h, pnet, ps, out, 3, logs, 5, w))) return rc;
+  for (int a = 0; a < 3 && CL; ++a)
+    for (int l = 0; l < CL; ++l)
+      MT_REQUIRE(h, !bytes_overlap(out[a].p, out[a].bytes, p->critic_weight[l], (size_t)cs.n_out[l] * cs.n_in[l] * 4) &&
+                        !bytes_overlap(out[a].p, out[a].bytes, p->critic_bias[l], (size_t)cs.n_out[l] * 4),
+                 w + "." + out[a].name + " overlaps critic_weight / critic_bias [" + std::to_string(l) + "]");
+  MT_ENTER(h);
+  ActorCriticArgs r{};
+  for (int l = 0; l < CL; ++l) {
+    r.cw[l] = p->critic_weight[l];
+    r.cb[l] = p->critic_bias[l];
+    r.c_n_in[l] = cs.n_in[l];
+    r.c_n_out[l] = cs.n_out[l];
+  }
+  r.CL = CL;
+  r.c_hidden_act = p->critic_hidden_act;
+  r.c_out_act = p->critic_out_act;
+  r.c_out_scale = p->critic_out_scale;
+  if (p->logp_log)
+    for (int j = 0; j < D; ++j) r.inv_var[j] = (float)(1.0 / ((double)q->sigma[j] * (double)q->sigma[j]));
+  r.logp_log = p->logp_log;
+  r.logp_ld = p->logp_ld;
+  r.value_log = p->value_log;
+  r.value_ld = p->value_ld;
+  r.last_value = p->last_value_out;
+  return rollout_policy_run(h, q, sc, 1u, 0, &r, c_widest);
 }
 
 int mt_gae(mt_handle h, const struct mt_gae* s) {

@@ -239,6 +239,11 @@ int join_chains(mt_handle h);
 // engine.hip: a full reset that mt_reset_random deferred into the next mt_rollout is launched now (no-op without one)
 int flush_pending_reset(mt_handle h);
 
+// actor_critic.hip: mt_rollout_actor_critic's launch (ActorCriticArgs: kernels.h) and the dynamic LDS it asks for
+struct ActorCriticArgs;
+size_t actor_critic_lds(const mt_engine* h, int n_in, bool critic);
+void launch_actor_critic(mt_handle h, const StepArgs& a, const ActorCriticArgs& r, int width);
+
 }  // namespace mt
 
 #define MT_HIP(h, call)                                                                            \

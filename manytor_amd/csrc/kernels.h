@@ -24,6 +24,9 @@
 
 namespace mt {
 
+// This header is included by more than one translation unit (engine.hip, actor_critic.hip: compiled side by side): every
+// definition in it is a template, a forceinline function or an `inline` kernel.
+
 // Write-only outputs of a step (observations, reward, done, end effector) are never re-read by the next
 // step.  MT_NT_STORES marks them non-temporal so they do not displace the re-read state (goals, targets,
 // alive mask, return) from L2 / Infinity Cache.
@@ -521,7 +524,7 @@ constexpr bool whole_degree_offsets() {
 // come after whatever the kernel can do in between (its pose loads, the Philox block).
 constexpr int kTrigVec4 = kTrigEntries * 2 / 4;  // the table as float4s
 static_assert(kTrigEntries * 2 % 4 == 0 && kTrigVec4 <= kBlock, "one float4 per thread stages the table");
-__global__ __launch_bounds__(kBlock) void fill_trig_table_kernel(float* table) {
+inline __global__ __launch_bounds__(kBlock) void fill_trig_table_kernel(float* table) {
   for (int idx = threadIdx.x; idx < kTrigEntries; idx += kBlock) {
     float sv, cv;
     sincos_deg((float)(idx - kTrigBias), sv, cv);
@@ -1606,7 +1609,7 @@ __global__ __launch_bounds__(kBlock) void trace_kernel(const StepArgs a, float* 
 
 // done_bits word `word` rebuilt from the done bytes: single-env launches (mt_env_step / mt_env_reset) cannot produce
 // the 64-env ballot themselves.  One wavefront.
-__global__ __launch_bounds__(64) void done_bits_word_kernel(const uint8_t* done, int64_t n, int64_t word,
+inline __global__ __launch_bounds__(64) void done_bits_word_kernel(const uint8_t* done, int64_t n, int64_t word,
                                                             unsigned long long* done_bits) {
   const int64_t i = word * 64 + threadIdx.x;
   const unsigned long long bits = __ballot(i < n && done[i] != 0);
@@ -1614,7 +1617,7 @@ __global__ __launch_bounds__(64) void done_bits_word_kernel(const uint8_t* done,
 }
 
 // All done_bits words rebuilt from the done bytes (mt_set(MT_F_DONE): restoring a checkpoint).
-__global__ __launch_bounds__(kBlock) void done_bits_rebuild_kernel(const uint8_t* done, int64_t n, unsigned long long* done_bits) {
+inline __global__ __launch_bounds__(kBlock) void done_bits_rebuild_kernel(const uint8_t* done, int64_t n, unsigned long long* done_bits) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
   const unsigned long long bits = __ballot(i < n && done[i] != 0);
   if ((threadIdx.x & 63) == 0 && (int64_t)i < n) done_bits[i >> 6] = bits;
@@ -1646,7 +1649,7 @@ __device__ __forceinline__ void draw_targets(uint64_t seed, uint64_t env_id, uin
 // ---------------------------------------------------------------------------
 // action_sample for all envs (manytor.py:215-217), device RNG.
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(kBlock) void sample_actions_kernel(float* actions, int64_t n, int64_t ld, int D,
+inline __global__ __launch_bounds__(kBlock) void sample_actions_kernel(float* actions, int64_t n, int64_t ld, int D,
                                                                 int64_t env_base, uint64_t seed, uint32_t step_idx) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;  // 32-bit lane offset: rows are addressed as uniform base + i
   if (i >= n) return;
@@ -2645,6 +2648,74 @@ __device__ __forceinline__ void policy_hidden(weight_ptr w, weight_ptr b, int n_
   }
 }
 
+// mt_rollout_actor_critic: what rollout_policy_kernel<.., AC = true> reads on top of PolicyArgs.  The critic is a second MLP
+// of the policy's shape with one output, on the same x; logp is policy_eval_kernel's sequence on the mean and the action
+// the step already holds.
+struct ActorCriticArgs : PolicyArgs {
+  const float* cw[3];
+  const float* cb[3];
+  int32_t c_n_in[3], c_n_out[3];  // per layer; c_n_in[0] = IN, c_n_out[CL - 1] = 1
+  int32_t CL;                     // the critic's layers, 0 = no critic
+  int32_t c_hidden_act, c_out_act;
+  float c_out_scale;
+  float inv_var[MT_MAX_DOF];  // the fp32 nearest to 1 / sigma_j^2 (read with logp_log)
+  float* logp_log;            // [T][logp_ld] or NULL
+  int64_t logp_ld;
+  float* value_log;  // [T][value_ld] or NULL
+  int64_t value_ld;
+  float* last_value;  // [n] or NULL
+};
+template <bool AC>
+struct PolicyRolloutMode {
+  using Args = PolicyArgs;
+};
+template <>
+struct PolicyRolloutMode<true> {
+  using Args = ActorCriticArgs;
+};
+
+// The critic on the x a lane parked in its LDS column (x_k = xcol[k kBlock]): policy_eval_kernel's forward pass with one
+// output, the same helpers over the same triples in the same order, so the value has mt_policy_eval's bits.
+template <int W>
+__device__ __forceinline__ float critic_value(const ActorCriticArgs& r, const float* xcol, int K, int n_pose) {
+  const int L = r.CL, IN = r.c_n_in[0];
+  const weight_ptr w0 = as_weights(r.cw[0]), b0 = as_weights(r.cb[0]);
+  const weight_ptr wl = as_weights(r.cw[L - 1]), bl = as_weights(r.cb[L - 1]);  // the output layer
+  auto first_layer = [&](auto& acc, int n_out) {
+    policy_bias(acc, b0, n_out);
+    for (int k = 0; k < K; ++k) {
+      float tri[3];
+#pragma unroll
+      for (int q = 0; q < 3; ++q) tri[q] = xcol[(3 * k + q) * kBlock];
+      policy_feed(acc, w0, IN, n_out, 3 * k, tri);
+    }
+    for (int j = 0; j < n_pose; ++j) {
+      const float xj[1] = {xcol[(3 * K + j) * kBlock]};
+      policy_feed(acc, w0, IN, n_out, 3 * K + j, xj);
+    }
+  };
+  float y;
+  if (L == 1) {
+    float y1[1];
+    first_layer(y1, 1);
+    y = y1[0];
+  } else {
+    float h0[W];
+    first_layer(h0, r.c_n_out[0]);
+    policy_finish(h0, r.c_hidden_act, r.c_n_out[0]);
+    if (L == 2) {
+      y = policy_dot<W>(wl, bl[0], r.c_n_in[1], h0);
+    } else {
+      float h1[W];
+#pragma unroll
+      for (int o = 0; o < W; ++o) h1[o] = 0.f;
+      policy_hidden<W>(as_weights(r.cw[1]), as_weights(r.cb[1]), r.c_n_in[1], r.c_n_out[1], r.c_hidden_act, h0, h1);
+      y = policy_dot<W>(wl, bl[0], r.c_n_in[2], h1);
+    }
+  }
+  return r.c_out_scale * policy_act(r.c_out_act, y);
+}
+
 // the observation frame's origin at pose g, as observe_kernel computes it
 template <int D>
 __device__ __forceinline__ void pose_obs_frame(const DhConst& dh, const float (&g)[D], float (&el)[3]) {
@@ -2656,9 +2727,13 @@ __device__ __forceinline__ void pose_obs_frame(const DhConst& dh, const float (&
   pick_frames<RtTableF<D>>(t, p, el, e_unused);
 }
 
-template <class Tbl, int W>
-__global__ __launch_bounds__(kBlock) void rollout_policy_kernel(const StepArgs a, const PolicyArgs r) {
-  extern __shared__ __attribute__((aligned(16))) float tile[];  // [3K][kBlock]
+// AC (mt_rollout_actor_critic): the same launch also writes log pi(a_t | x_t) and the critic's V(x_t) per step and V(x_T)
+// at the end.  x is parked in a lane-private LDS column behind the target tile while it streams through the policy's first
+// layer, and the critic runs from there once the policy's hidden vectors are dead: no barrier, no second observation, and
+// no more than the policy's own two register arrays live at a time.
+template <class Tbl, int W, bool AC = false>
+__global__ __launch_bounds__(kBlock) void rollout_policy_kernel(const StepArgs a, const typename PolicyRolloutMode<AC>::Args r) {
+  extern __shared__ __attribute__((aligned(16))) float tile[];  // [3K][kBlock]; AC with a critic: [IN][kBlock] behind it
   constexpr int D = Tbl::D;
   const Tbl t = TableMaker<Tbl>::make(a.dh);
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
@@ -2695,28 +2770,44 @@ __global__ __launch_bounds__(kBlock) void rollout_policy_kernel(const StepArgs a
     pose_obs_frame<D>(a.dh, zero, el_zero);
   }
 
-  // the policy's input at the state the step starts from, streamed into the first layer's accumulators
-  auto first_layer = [&](auto& acc, int n_out, int s) {
-    policy_bias(acc, b0, n_out);
+  // the policy's input at the state a step starts from, handed to `use` piece by piece (row s of `olog` gets it, if given)
+  auto each_x = [&](int s, float* olog, auto&& use) {
     for (int k = 0; k < a.K; ++k) {
       float x, y, z, tri[3] = {0.f, 0.f, 0.f};
       tc.get(k, x, y, z);
       if ((am >> k) & 1u) observe_target(el_cur, x, y, z, tri[0], tri[1], tri[2]);
-      if (r.obs_log) {
-        float* orow = r.obs_log + ((int64_t)s * IN + 3 * k) * r.obs_ld;
+      if (olog) {
+        float* orow = olog + ((int64_t)s * IN + 3 * k) * r.obs_ld;
 #pragma unroll
         for (int q = 0; q < 3; ++q) str_stream(orow + q * r.obs_ld, o4, tri[q]);
       }
-      policy_feed(acc, w0, IN, n_out, 3 * k, tri);
+      use(3 * k, tri);
     }
     if (r.see_pose) {
 #pragma unroll
       for (int j = 0; j < D; ++j) {
-        if (r.obs_log) str_stream(r.obs_log + ((int64_t)s * IN + 3 * a.K + j) * r.obs_ld, o4, g[j]);
+        if (olog) str_stream(olog + ((int64_t)s * IN + 3 * a.K + j) * r.obs_ld, o4, g[j]);
         const float xj[1] = {g[j]};
-        policy_feed(acc, w0, IN, n_out, 3 * a.K + j, xj);
+        use(3 * a.K + j, xj);
       }
     }
+  };
+  // AC: rows k .. of the lane's x column in LDS (written and read by this lane only)
+  float* const xcol = tile + 3 * a.K * kBlock + threadIdx.x;
+  auto park = [&](int k, const auto& x) {
+    constexpr int NX = sizeof(x) / sizeof(float);
+#pragma unroll
+    for (int q = 0; q < NX; ++q) xcol[(k + q) * kBlock] = x[q];
+  };
+  // ... streamed into the first layer's accumulators
+  auto first_layer = [&](auto& acc, int n_out, int s) {
+    policy_bias(acc, b0, n_out);
+    each_x(s, r.obs_log, [&](int k, const auto& x) {
+      policy_feed(acc, w0, IN, n_out, k, x);
+      if constexpr (AC) {
+        if (r.CL) park(k, x);
+      }
+    });
   };
 
   for (int s = 0; s < r.T; ++s) {
@@ -2742,6 +2833,7 @@ __global__ __launch_bounds__(kBlock) void rollout_policy_kernel(const StepArgs a
           for (int j = 0; j < D; ++j) y[j] = policy_dot<W>(wl + (int64_t)j * r.n_in[2], bl[j], r.n_in[2], h1);
         }
       }
+      [[maybe_unused]] float lp = 0.f;  // AC: policy_eval_kernel's chain over (a_j - mu_j)^2 / sigma_j^2
       uint32_t nw[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
       if (r.noisy) {
         const u32x4 n0 = stream_block(seed, env_id, kTagPolicy, r.draw, plan_minor(0u, 0u, (uint32_t)s));
@@ -2754,13 +2846,30 @@ __global__ __launch_bounds__(kBlock) void rollout_policy_kernel(const StepArgs a
 #pragma unroll
       for (int j = 0; j < D; ++j) {
         float v = r.out_scale * policy_act(r.out_act, y[j]);
+        [[maybe_unused]] const float mu = v;
         if (r.noisy && r.sigma[j] > 0.f) {
           const float sz = r.sigma[j] * plan_noise(nw[j]);
           v = v + sz;
         }
         raw[j] = unusable_angle(v) ? v : fminf(fmaxf(v, r.lo), r.hi);
         if (r.action_log) str_stream(r.action_log + ((int64_t)s * D + j) * r.act_ld, o4, raw[j]);
+        if constexpr (AC) {
+          const float e = raw[j] - mu;
+          const float d = e * r.inv_var[j];
+          lp = __builtin_fmaf(e, d, lp);
+        }
       }
+      if constexpr (AC) {
+        if (r.logp_log) {
+          bool unusable = false;
+#pragma unroll
+          for (int j = 0; j < D; ++j) unusable |= unusable_angle(raw[j]);
+          str_stream(r.logp_log + (int64_t)s * r.logp_ld, o4, unusable ? 0.f : -0.5f * lp);
+        }
+      }
+    }
+    if constexpr (AC) {  // V(x_s): the policy's h0 / h1 are dead, x sits in the lane's LDS column
+      if (r.value_log) str_stream(r.value_log + (int64_t)s * r.value_ld, o4, critic_value<W>(r, xcol, a.K, IN - 3 * a.K));
     }
     bool bad = false;
 #pragma unroll
@@ -2834,6 +2943,12 @@ __global__ __launch_bounds__(kBlock) void rollout_policy_kernel(const StepArgs a
   }
 
   if (r.return_out) str_stream(r.return_out, o4, ret);
+  if constexpr (AC) {  // V(x_T): the input a step T would start from (after a re-arm in the last step: the zero pose, new targets)
+    if (r.last_value) {
+      each_x(r.T, (float*)nullptr, park);
+      str_stream(r.last_value, o4, critic_value<W>(r, xcol, a.K, IN - 3 * a.K));
+    }
+  }
   if (!commit) return;
 #pragma unroll
   for (int j = 0; j < D; ++j) str(a.goals + j * ld, o4, g[j]);
@@ -2884,7 +2999,7 @@ __device__ __forceinline__ uint32_t es_word(uint64_t seed, uint32_t p, uint32_t 
   return q == 0u ? b.x : q == 1u ? b.y : q == 2u ? b.z : b.w;
 }
 
-__global__ __launch_bounds__(kBlock) void es_sample_kernel(const EsArgs r) {
+inline __global__ __launch_bounds__(kBlock) void es_sample_kernel(const EsArgs r) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= r.P) return;
   const uint32_t p = blockIdx.y;
@@ -2896,7 +3011,7 @@ __global__ __launch_bounds__(kBlock) void es_sample_kernel(const EsArgs r) {
   row[r.pitch] = th - se;
 }
 
-__global__ __launch_bounds__(kBlock) void es_sums_kernel(const EsArgs r) {
+inline __global__ __launch_bounds__(kBlock) void es_sums_kernel(const EsArgs r) {
   __shared__ long long part[kBlock / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int m = blockIdx.x;  // (the grid is M blocks)
@@ -2916,7 +3031,7 @@ __global__ __launch_bounds__(kBlock) void es_sums_kernel(const EsArgs r) {
   }
 }
 
-__global__ __launch_bounds__(kBlock) void es_update_kernel(const EsArgs r) {
+inline __global__ __launch_bounds__(kBlock) void es_update_kernel(const EsArgs r) {
   extern __shared__ __attribute__((aligned(16))) long long es_lds[];  // [M] sums, [M / 2] coefficients
   const int M = r.M;
   long long* es_sum = es_lds;
@@ -3423,7 +3538,7 @@ __global__ __launch_bounds__(kBlock) void policy_grad_kernel(const typename Poli
 }
 
 // grad[i] = scale * (partials[0][i] + partials[1][i] + ...), ascending; word P is the loss
-__global__ __launch_bounds__(kBlock) void policy_grad_reduce_kernel(const PolicyGradArgs r) {
+inline __global__ __launch_bounds__(kBlock) void policy_grad_reduce_kernel(const PolicyGradArgs r) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i > r.P) return;
   float s = 0.f;
@@ -3434,7 +3549,7 @@ __global__ __launch_bounds__(kBlock) void policy_grad_reduce_kernel(const Policy
 }
 
 // mt_ppo_grad's second pass: the same sums over rows of P + 1 + kPpoExtras words; the last two words are integer counts
-__global__ __launch_bounds__(kBlock) void ppo_grad_reduce_kernel(const PpoGradArgs r) {
+inline __global__ __launch_bounds__(kBlock) void ppo_grad_reduce_kernel(const PpoGradArgs r) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int64_t pitch = r.P + 1 + kPpoExtras;
   if (i >= pitch) return;
@@ -3466,7 +3581,7 @@ struct RewardToGoArgs {
   uint32_t mask_after_done;
 };
 // one lane per env, backwards over t: R_t = fmaf(gamma, done_t ? 0 : R_t+1, r_t); steps behind the first done are 0 when masked
-__global__ __launch_bounds__(kBlock) void reward_to_go_kernel(const RewardToGoArgs r) {
+inline __global__ __launch_bounds__(kBlock) void reward_to_go_kernel(const RewardToGoArgs r) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= r.n) return;
   int first = r.T;
@@ -3599,7 +3714,7 @@ struct GaeArgs {
 };
 // one lane per env, backwards over t, as reward_to_go_kernel: delta = fmaf(gamma, done_t ? 0 : V_t+1, r_t) - V_t,
 // A_t = fmaf(gl, done_t ? 0 : A_t+1, delta), ret_t = A_t + V_t; steps behind the first done are 0 (and not read) when masked
-__global__ __launch_bounds__(kBlock) void gae_kernel(const GaeArgs r) {
+inline __global__ __launch_bounds__(kBlock) void gae_kernel(const GaeArgs r) {
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= r.n) return;
   int first = r.T;
@@ -4522,14 +4637,14 @@ __global__ __launch_bounds__(kBlock) void soa_to_soa_f32(const S* src, int rows,
   for (int r = 0; r < rows; ++r) (dst + (int64_t)r * ld)[i] = (float)(src + (int64_t)r * ld)[i];
 }
 
-__global__ __launch_bounds__(kBlock) void alive_unpack(const uint32_t* mask, int K, int64_t n, uint8_t* dst) {
+inline __global__ __launch_bounds__(kBlock) void alive_unpack(const uint32_t* mask, int K, int64_t n, uint8_t* dst) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;  // 32-bit lane offset: rows are addressed as uniform base + i
   if (i >= n) return;
   const uint32_t m = mask[i];
   for (int k = 0; k < K; ++k) dst[(int64_t)i * K + k] = (m >> k) & 1u;
 }
 
-__global__ __launch_bounds__(kBlock) void alive_pack(const uint8_t* src, int K, int64_t n, uint32_t* mask) {
+inline __global__ __launch_bounds__(kBlock) void alive_pack(const uint8_t* src, int K, int64_t n, uint32_t* mask) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;  // 32-bit lane offset: rows are addressed as uniform base + i
   if (i >= n) return;
   uint32_t m = 0;
@@ -4548,7 +4663,7 @@ struct FkArgs {
   DhConst dh;
 };
 
-__global__ __launch_bounds__(kBlock) void fk_kernel(const FkArgs a) {
+inline __global__ __launch_bounds__(kBlock) void fk_kernel(const FkArgs a) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;  // 32-bit lane offset: rows are addressed as uniform base + i
   if (i >= a.n) return;
   float X[3] = {1.f, 0.f, 0.f}, Y[3] = {0.f, 1.f, 0.f}, Z[3] = {0.f, 0.f, 1.f}, o[3] = {0.f, 0.f, 0.f};
@@ -4591,7 +4706,7 @@ struct TraceArgs {
   DhConst dh;
 };
 
-__global__ __launch_bounds__(kBlock) void route_trace_kernel(const TraceArgs a) {
+inline __global__ __launch_bounds__(kBlock) void route_trace_kernel(const TraceArgs a) {
   const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (gid >= a.n * a.S) return;
   const int64_t env = gid / a.S;
@@ -4624,7 +4739,7 @@ __global__ __launch_bounds__(kBlock) void route_trace_kernel(const TraceArgs a) 
   }
 }
 
-__global__ __launch_bounds__(kBlock) void r_theta_kernel(const float* v1, const float* v2, int64_t n, float* out) {
+inline __global__ __launch_bounds__(kBlock) void r_theta_kernel(const float* v1, const float* v2, int64_t n, float* out) {
   const uint32_t i = blockIdx.x * kBlock + threadIdx.x;  // 32-bit lane offset: rows are addressed as uniform base + i
   if (i >= n) return;
   const int64_t b3 = 3 * (int64_t)i;

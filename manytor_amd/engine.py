@@ -541,7 +541,8 @@ class StepEngine:
 
     def rollout_policy(self, layers, steps, *, hidden="tanh", out="tanh", out_scale=180.0, see_pose=False, sigma=None, draw=0,
                        seed=0x5EED, auto_reset=False, lo=-180., hi=180., log=False, returns=False, actions=False,
-                       observations=False, dry_run=False):
+                       observations=False, dry_run=False, logp=False, critic=None, critic_hidden="tanh", critic_out="identity",
+                       critic_out_scale=1.0):
         """`steps` steps driven by an MLP policy in ONE launch (mt_rollout_policy): at every step each env's observation at
         the state it is in (the 3K floats observe() would give; see_pose=True appends the D joint angles) goes through
         `layers` -- a list of (weight, bias) CUDA float32 tensors in torch.nn.Linear layout, read in place, or a
@@ -551,7 +552,12 @@ class StepEngine:
         state afterwards is what rollout_actions leaves for the logged actions.  Returns a dict of device tensors (None
         when nothing is asked for): log -> `reward` (T, N) int8, `done` (T, N) uint8; returns -> `returns` (N,);
         actions -> `actions` (T, D, N); observations -> `observations` (T, IN, N).  dry_run=True evaluates only.
-        Stream behaviour as rollout_actions."""
+        logp=True and / or critic= (a value head as `layers` is given, on the same input: unflatten_value's views, or a
+        Sequential; critic_hidden / critic_out / critic_out_scale as values() takes them) make it the actor-critic
+        collection, still ONE launch (mt_rollout_actor_critic): `logp` (T, N) is policy_eval's logp of the logged actions
+        under `sigma` (every entry > 0 then), `values` (T, N) is values() of the logged observations and `last_value`
+        (N,) the critic on the state behind the last step -- what gae() takes -- each bit for bit, with neither log
+        needed.  A critic needs 3K + IN <= 160.  Stream behaviour as rollout_actions."""
         import torch
         if auto_reset and dry_run:
             raise ValueError("dry_run and auto_reset exclude each other: the re-arm writes the return ring")
@@ -566,7 +572,11 @@ class StepEngine:
             raise ValueError(f"steps must be 0..65535, got {T}")
         dev = torch.device("cuda", self.device)
         n_in = 3 * self.obj_number + (d if see_pose else 0)
-        arg = L.MtPolicy()
+        if not (logp or critic is not None):
+            arg = L.MtPolicy()
+        else:
+            full = L.MtActorCritic()
+            arg = full.policy
         keep = []
         fan_in = n_in
         for l, (w, b) in enumerate(pairs):
@@ -614,9 +624,62 @@ class StepEngine:
         arg.return_out = res["returns"].data_ptr() if returns else None
         arg.seed = int(seed)
         arg.reserved = 0
-        self._torch_call(self._lib.mt_rollout_policy, C.byref(arg), commits=not dry_run)
+        if not (logp or critic is not None):
+            self._torch_call(self._lib.mt_rollout_policy, C.byref(arg), commits=not dry_run)
+            del keep
+            return res or None
+        full.struct_size = C.sizeof(L.MtActorCritic)
+        if logp:
+            if not (np.isfinite(sig[:d]).all() and (sig[:d] > 0).all()):
+                raise ValueError(f"logp needs sigma: D entries, finite and > 0, got {sigma!r}")
+            res["logp"] = torch.empty((T, n), dtype=torch.float32, device=dev)
+            full.logp_log, full.logp_ld = (res["logp"].data_ptr() if T else None), n
+        if critic is not None:
+            for name, v, allowed in (("critic_hidden", critic_hidden, ("tanh", "relu")), ("critic_out", critic_out, ("tanh", "identity"))):
+                if v not in allowed:
+                    raise ValueError(f"{name} must be one of {allowed}, got {v!r}")
+            if not np.isfinite(np.float32(critic_out_scale)):
+                raise ValueError("critic_out_scale must be finite")
+            keep += self._critic_arg(full, critic, critic_hidden, critic_out, n_in)
+            full.critic_out_scale = float(critic_out_scale)
+            res["values"] = torch.empty((T, n), dtype=torch.float32, device=dev)
+            res["last_value"] = torch.empty(n, dtype=torch.float32, device=dev)
+            full.value_log, full.value_ld = (res["values"].data_ptr() if T else None), n
+            full.last_value_out = res["last_value"].data_ptr() if T else None
+        full.reserved = 0
+        if T:                                                    # (no step: nothing to write, and no address to hand over)
+            self._torch_call(self._lib.mt_rollout_actor_critic, C.byref(full), commits=not dry_run)
         del keep
-        return res or None
+        return res
+
+    def _critic_arg(self, full, critic, hidden, out, n_in):
+        """The value head of rollout_policy's `critic` into `full` (critic_layers, widths, activations, weight, bias): the
+        policy's layout and limits with one output.  -> the tensors to keep alive."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        pairs = self._policy_layers(critic, hidden, out)
+        if not 1 <= len(pairs) <= L.POLICY_MAX_LAYERS:
+            raise ValueError(f"critic: a value head has 1..{L.POLICY_MAX_LAYERS} linear layers, got {len(pairs)}")
+        keep, fan_in = [], n_in
+        for l, (w, b) in enumerate(pairs):
+            w, b = w.detach(), b.detach()
+            fan_out = 1 if l == len(pairs) - 1 else int(w.shape[0]) if w.dim() == 2 else -1
+            if tuple(w.shape) != (fan_out, fan_in) or tuple(b.shape) != (fan_out,):
+                raise ValueError(f"critic layer {l}: weight must be ({fan_out if fan_out > 0 else 'out'}, {fan_in}) and bias (out,), "
+                                 f"got {tuple(w.shape)} and {tuple(b.shape)}")
+            if l < len(pairs) - 1 and not 1 <= fan_out <= L.POLICY_MAX_WIDTH:
+                raise ValueError(f"critic layer {l}: width must be 1..{L.POLICY_MAX_WIDTH}, got {fan_out}")
+            for what, t in (("weight", w), ("bias", b)):
+                if t.dtype != torch.float32 or not t.is_cuda or t.device != dev or not t.is_contiguous():
+                    raise ValueError(f"critic layer {l}: {what} must be a contiguous float32 tensor on {dev}")
+            keep += [w, b]
+            full.critic_weight[l], full.critic_bias[l] = w.data_ptr(), b.data_ptr()
+            if l < len(pairs) - 1:
+                full.critic_width[l] = fan_out
+            fan_in = fan_out
+        full.critic_layers = len(pairs)
+        full.critic_hidden_act, full.critic_out_act = self._ACTIVATIONS[hidden], self._ACTIVATIONS[out]
+        return keep
 
     # ---- evolution strategies: a population of policies, one row of flat parameters per member ----------------------------
     def _policy_shapes(self, widths, see_pose=False, n_out=None):

@@ -15,9 +15,12 @@ from manytor_amd import build as B  # noqa: E402
 def main():
     flt = sys.argv[1:]
     with tempfile.TemporaryDirectory() as td:
-        cmd = [B._hipcc(), "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-c", "-I", B.INCLUDE, *B.EXTRA_FLAGS,
-               "-Rpass-analysis=kernel-resource-usage", os.path.join(B.CSRC, "engine.hip"), "-o", os.path.join(td, "e.o")]
-        txt = subprocess.run(cmd, capture_output=True, text=True).stderr
+        procs = []
+        for src in B.SOURCES:                        # side by side, as the build compiles them
+            cmd = [B._hipcc(), "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-c", "-I", B.INCLUDE, *B.EXTRA_FLAGS,
+                   "-Rpass-analysis=kernel-resource-usage", os.path.join(B.CSRC, src), "-o", os.path.join(td, src + ".o")]
+            procs.append(subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True))
+        txt = "".join(p.communicate()[1] for p in procs)
     blocks = re.split(r"remark: [^\n]*Function Name: ", txt)[1:]
     names = [b.split("\n")[0].strip() for b in blocks]
     dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
